@@ -3,7 +3,14 @@
 (BASELINE.json configs[2] / metric), one step = one pass of the hot path over
 2 channels x 2^24 samples of synthetic 48 kHz white noise resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs the clock-settle and the W warm-up steps, times the
+K steps and prints the line (`value`, `ms_per_step`, the configuration).
+--dump-outputs DIR also writes what the last timed step computed as .npy
+files.  --full adds everything measured or checked beside the headline figure:
+parity against exact products and the oracle, the CPU baselines, per-kernel
+and roofline figures, the host-buffer rate and the other configs' legs.
 
 N > 1 (torchrun, one rank per GPU): config 4's shard (BASELINE.json
 configs[3]): every rank convolves its own group of 8 channels x 2^24 samples
@@ -41,6 +48,16 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--samples", type=int, default=None,
                    help="samples per channel per step (default 2^24)")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the parity checks against exact "
+                        "products and the oracle, the CPU baselines, the per-kernel and roofline passes, the "
+                        "host-buffer rate, the N > 1 conv-only pass and the other configs' legs (the options "
+                        "below that select among them apply only with --full).  Without it a run sets up, "
+                        "settles and warms up, times the K steps, writes --dump-outputs and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (the arrays its caller "
+                        "receives) as DIR/<name>.npy in float64; an output larger than the budget is written as a "
+                        "fixed, seeded sample of its columns with the sample's positions in DIR/<name>_index.npy")
     p.add_argument("--hop", type=int, default=8192)
     p.add_argument("--chunk", type=int, default=0, help="blocks per channel per engine chunk (0 = auto)")
     p.add_argument("--schedule", choices=["serial", "pipelined", "chunked"], default="serial",
@@ -309,6 +326,46 @@ def exact_window(x, h, t0, w):
     return np.convolve(seg, h, mode="valid")
 
 
+DUMP_BUDGET = 48 << 20  # bytes per --dump-outputs directory, index files included
+DUMP_EDGE = 4096        # columns kept whole at either end of a sampled output
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: each of `arrays` (name -> [rows][n] or [n], a torch tensor
+    on any device or a numpy array) as dirname/<name>.npy in float64.  The
+    budget is shared evenly; an array over its share is written as a sample of
+    its columns, the same for every row: the first and last DUMP_EDGE columns
+    and columns drawn by a generator seeded with the array's width, so two runs
+    with the same arguments sample the same positions.  The positions go to
+    dirname/<name>_index.npy.  Runs after the timed region."""
+    import numpy as np
+
+    out = pathlib.Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, a in arrays.items():
+        is_torch = hasattr(a, "index_select")
+        a = a.reshape(-1, a.shape[-1])
+        rows, n = a.shape
+        idx = None
+        if rows * n * 8 > share:
+            m = max(1, share // (8 * (rows + 1)))
+            edge = min(DUMP_EDGE, m // 4)
+            draw = np.random.default_rng(0x5EED ^ n).integers(0, n, size=m - 2 * edge, dtype=np.int64)
+            idx = np.unique(np.concatenate([np.arange(edge), draw, np.arange(n - edge, n)]))
+        if is_torch:
+            if idx is not None:
+                import torch
+
+                a = a.index_select(1, torch.from_numpy(idx).to(a.device))
+            a = a.cpu().numpy()
+        elif idx is not None:
+            a = a[:, idx]
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
+        if idx is not None:
+            np.save(out / f"{name}_index.npy", idx.astype(np.float64))
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -353,28 +410,40 @@ def conv_main(args, rt, world, rank, local):
     if args.samples is None:
         args.samples = 1 << 24
     ir = irlib.large_church()                       # [2][131072], Large Church zero padded
+    full = args.full
+    # without --full: no kernel events, no passes after the timed region
+    mode = args.kernel_timing if full else "off"
     r = run_conv(args, world, rank, rt, ir, args.channels, shard_cfg, mixdown, args.steps, args.warmup,
-                 args.kernel_timing, args.settle_steps, args.clock_settle)
+                 mode, args.settle_steps if full else 0, args.clock_settle, extras=full)
     C, n, K, out_len = args.channels, args.samples, ir.shape[1], r["out_len"]
-    elapsed, prof, prof_live, mode = r["elapsed"], r["prof"], r["prof_live"], args.kernel_timing
+    elapsed, prof, prof_live = r["elapsed"], r["prof"], r["prof_live"]
     ids, x_host, eng, ys, mixes, last = r["ids"], r["x_host"], r["eng"], r["ys"], r["mixes"], r["last"]
     comm = r["comm"]
 
     total_samples = world * C * n * args.steps
     value = total_samples / elapsed / 1e6
 
-    # dominant kernel + its roofline (algorithmic bytes / mean launch duration)
-    dom = max(prof, key=lambda k: prof[k][0])
-    if mode == "dominant":
-        dom = next(k for k, v in prof_live.items() if v[1] > 0)
-    ms, launches, alg_bytes = prof[dom]
-    avg_ms = ms / max(launches, 1)
-    achieved = (alg_bytes / max(launches, 1)) / (avg_ms * 1e-3) / 1e9
-    kernels = {k: {"avg_us": v[0] / max(v[1], 1) * 1e3, "launches": v[1],
-                   "alg_GBps": (v[2] / max(v[1], 1)) / (v[0] / max(v[1], 1) * 1e-3) / 1e9 if v[0] else None,
-                   "share": v[0] / max(sum(p[0] for p in prof.values()), 1e-12)} for k, v in prof.items()}
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the stereo mix (the whole
+        # job's on rank 0) when the mixdown runs, else this rank's channels.  The
+        # passes --full adds after the timed region rerun the same step on the
+        # same input, so the buffer holds the same values either way.
+        dump_outputs(args.dump_outputs, {"mix" if mixdown else "y": (mixes if mixdown else ys)[last]})
 
-    if rank == 0:
+    if rank == 0 and not full:
+        print(json.dumps(conv_line(args, r, world, C, n, K, value, elapsed, shard_cfg, mixdown)), flush=True)
+    if rank == 0 and full:
+        # dominant kernel + its roofline (algorithmic bytes / mean launch duration)
+        dom = max(prof, key=lambda k: prof[k][0])
+        if mode == "dominant":
+            dom = next(k for k, v in prof_live.items() if v[1] > 0)
+        ms, launches, alg_bytes = prof[dom]
+        avg_ms = ms / max(launches, 1)
+        achieved = (alg_bytes / max(launches, 1)) / (avg_ms * 1e-3) / 1e9
+        kernels = {k: {"avg_us": v[0] / max(v[1], 1) * 1e3, "launches": v[1],
+                       "alg_GBps": (v[2] / max(v[1], 1)) / (v[0] / max(v[1], 1) * 1e-3) / 1e9 if v[0] else None,
+                       "share": v[0] / max(sum(p[0] for p in prof.values()), 1e-12)} for k, v in prof.items()}
+
         # Parity of the measured output itself: windows of the last step's
         # result (the whole-job stereo mix on rank 0 when the mixdown runs)
         # against exact float64 dot products -- the signal start, a K2 run
@@ -474,39 +543,8 @@ def conv_main(args, rt, world, rank, local):
                     step_pmc = sum(tab[k]["hbm_bytes_per_launch"] for k in ks) if len(ks) == 3 else None
             except Exception:
                 traffic = None
-        workload = ("OverlapSave partitioned conv, stereo, 131072-tap IR, full linear convolution, "
-                    "input and output device-resident (PCIe excluded; host_io is the host-buffer rate) "
-                    if not shard_cfg else
-                    f"{C * world}-channel x 131072-tap IR convolution reverb (IR[c mod 2]), channels "
-                    f"sharded {C}-per-GPU, device-resident (PCIe excluded)" +
-                    ((", stereo mixdown fused into the inverse transform" if args.mix_fused == "on" else
-                      ", k_mixdown") + " + RCCL reduce (ad_mixdown_reduce) " if mixdown else " "))
-        line = {
-            "metric": "Msamples/sec, overlap-save conv 131072-tap IR @48kHz; achieved HBM GB/s",
-            "value": round(value, 3),
-            "unit": "Msamples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "clock_settle_steps": args.clock_settle,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic: SplitMix64 white noise (seed 0x5EED+channel) x Large Church IR from web/irs.irlib "
-                    "(f16, reference decodeF16), zero padded 95432->131072 taps",
-            "config": {
-                "workload": workload + f"({C} ch x {n} samples per GPU per step)",
-                "baseline_config": "configs[3] shard" if shard_cfg else "configs[2]",
-                "channels_per_gpu": C,
-                "samples_per_channel": n,
-                "kernel_taps": K,
-                "hop": args.hop,
-                "partitions": (K + args.hop - 1) // args.hop,
-                "schedule": {"mode": ["serial", "pipelined", "chunked"][r["schedule"][0]], "chunk_blocks": r["schedule"][1]},
-                "parallelism": f"channel-group per GPU x{world}" + (" + RCCL reduce mixdown" if mixdown else ""),
-            },
+        line = conv_line(args, r, world, C, n, K, value, elapsed, shard_cfg, mixdown)
+        line.update({
             "roofline": {
                 "kernel": dom,
                 "bound": "hbm",
@@ -527,7 +565,7 @@ def conv_main(args, rt, world, rank, local):
             "host_io": host_io,
             "shard_per_gpu": shard_sub,
             "cpu_baseline": cpu,
-        }
+        })
         if step_pmc:
             alg = 80 * C * n  # x in, y out, X and Z written and read: 8 + 8 + 32 + 32 B per sample
             sec = elapsed / args.steps
@@ -537,8 +575,6 @@ def conv_main(args, rt, world, rank, local):
                                 "note": "whole step at ms_per_step against 8 TB/s: PMC bytes of K1 + K2 + K3 "
                                         "(profiles/pmc_traffic.json, FETCH_SIZE x 2 + WRITE_SIZE) and the 80 B/sample "
                                         "algorithmic figure"}
-        if r["step_ms"]:
-            line["step_ms"] = r["step_ms"]  # each timed step, event-timed on the launch stream
         if r["settled"]:
             line["settled"] = dict(r["settled"], value=round(C * n / (r["settled"]["median_ms_last_half"] * 1e-3) / 1e6, 3),
                                    note="the same step after the timed region once the board's clock has recovered "
@@ -567,6 +603,51 @@ def conv_main(args, rt, world, rank, local):
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+def conv_line(args, r, world, C, n, K, value, elapsed, shard_cfg, mixdown):
+    """The conv / shard line's own keys: the headline figure of the timed steps and
+    the configuration they ran (conv_main adds what --full measures beside it)."""
+    workload = ("OverlapSave partitioned conv, stereo, 131072-tap IR, full linear convolution, "
+                "input and output device-resident (PCIe excluded; host_io is the host-buffer rate) "
+                if not shard_cfg else
+                f"{C * world}-channel x 131072-tap IR convolution reverb (IR[c mod 2]), channels "
+                f"sharded {C}-per-GPU, device-resident (PCIe excluded)" +
+                ((", stereo mixdown fused into the inverse transform" if args.mix_fused == "on" else
+                  ", k_mixdown") + " + RCCL reduce (ad_mixdown_reduce) " if mixdown else " "))
+    line = {
+        "metric": "Msamples/sec, overlap-save conv 131072-tap IR @48kHz; achieved HBM GB/s",
+        "value": round(value, 3),
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "clock_settle_steps": args.clock_settle,
+        "full": bool(args.full),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic: SplitMix64 white noise (seed 0x5EED+channel) x Large Church IR from web/irs.irlib "
+                "(f16, reference decodeF16), zero padded 95432->131072 taps",
+        "config": {
+            "workload": workload + f"({C} ch x {n} samples per GPU per step)",
+            "baseline_config": "configs[3] shard" if shard_cfg else "configs[2]",
+            "channels_per_gpu": C,
+            "samples_per_channel": n,
+            "kernel_taps": K,
+            "hop": args.hop,
+            "partitions": (K + args.hop - 1) // args.hop,
+            "schedule": {"mode": ["serial", "pipelined", "chunked"][r["schedule"][0]], "chunk_blocks": r["schedule"][1]},
+            "parallelism": f"channel-group per GPU x{world}" + (" + RCCL reduce mixdown" if mixdown else ""),
+        },
+    }
+    if r["step_ms"]:
+        line["step_ms"] = r["step_ms"]  # each timed step, event-timed on the launch stream
+    if args.dump_outputs:
+        line["dump_outputs"] = args.dump_outputs
+    return line
 
 
 def output_parity(args, r, ir, C_total, mixdown):
@@ -613,11 +694,15 @@ def output_parity(args, r, ir, C_total, mixdown):
     return parity
 
 
-def run_conv(args, world, rank, rt, ir, C, shard_cfg, mixdown, steps, warmup, mode, settle_steps=0, pre_steps=0):
+def run_conv(args, world, rank, rt, ir, C, shard_cfg, mixdown, steps, warmup, mode, settle_steps=0, pre_steps=0,
+             extras=True):
     """One conv measurement: C channels x args.samples per GPU per step (IR[c mod 2]),
     optionally with the RCCL stereo mixdown; `steps` timed steps after `warmup`,
     bracketed by barrier + synchronize, max over ranks.  Returns the timing, the
-    per-kernel event profile and the buffers for the parity check.  `rt`
+    per-kernel event profile and the buffers for the parity check.  With
+    `extras` off (a run without --full; `mode` is then "off") nothing runs after
+    the timed region: no per-kernel pass, no conv-only pass, so `prof` is empty
+    and `reduce_diag` is None.  `rt`
     supplies the device, streams, events, the engine and the communicator
     (GpuRuntime; a CPU stand-in in tests/test_bench_orchestration.py)."""
     import numpy as np
@@ -747,7 +832,9 @@ def run_conv(args, world, rank, rt, ir, C, shard_cfg, mixdown, steps, warmup, mo
     reduce_ms = sum(a.elapsed_time(b) for a, b in red_ev) / steps if red_ev else 0.0
     red_ev.clear()
     prof_live = eng.profile_read() if mode != "off" else {}
-    if mode != "on":  # the kernels not timed live: a separate event-timed pass
+    if not extras:
+        prof = prof_live
+    elif mode != "on":  # the kernels not timed live: a separate event-timed pass
         eng.profile_enable(True)
         for _ in range(max(2, steps // 2)):
             step()
@@ -763,7 +850,7 @@ def run_conv(args, world, rank, rt, ir, C, shard_cfg, mixdown, steps, warmup, mo
     eng.profile_enable(False)
 
     conv_elapsed = None
-    if mixdown:
+    if mixdown and extras:
         # the same step with the reduce off: what the convolution alone takes
         # (N > 1 diagnostics: does the reduce hide?)
         reduce_on[0] = False
@@ -793,7 +880,7 @@ def run_conv(args, world, rank, rt, ir, C, shard_cfg, mixdown, steps, warmup, mo
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, conv_elapsed, reduce_ms = (float(v) for v in t.tolist())
     diag = None
-    if mixdown:
+    if mixdown and extras:
         diag = shard.scaling_diagnostics(elapsed / steps * 1e3, conv_elapsed / steps * 1e3, reduce_ms,
                                          2 * out_len * 8)
 
@@ -820,12 +907,13 @@ def run_conv(args, world, rank, rt, ir, C, shard_cfg, mixdown, steps, warmup, mo
             "reduce_diag": diag, "step_ms": step_ms, "settled": settled}
 
 
-def stream_measure(nblk: int, warmup_blocks: int, cpu_leg: bool) -> dict:
+def stream_measure(nblk: int, warmup_blocks: int, cpu_leg: bool, parity_on: bool = True, dump=None) -> dict:
     """BASELINE config 2: StreamingOverlapSave(K=16384, B=4096) driven block by
     block through the host-buffer ABI, as a Go caller would (ProcessBlockTo per
     block: PCIe in, UPOLS on the GPU, PCIe out, synchronous; reference
     streaming_overlap_save.go:100-164).  Per-block wall times give p50 / p99;
-    parity: the measured output's first blocks against exact float64 products."""
+    parity: the measured output's first blocks against exact float64 products.
+    `dump`: a --dump-outputs directory for the timed blocks' output."""
     import numpy as np
 
     from algodsp import conv, irlib, signals
@@ -846,14 +934,18 @@ def stream_measure(nblk: int, warmup_blocks: int, cpu_leg: bool) -> dict:
         lat[i] = time.perf_counter() - tb
     dt = time.perf_counter() - t0
     hits, timeouts = s.LowLatencyStats()
-    nchk = min(nblk, 4) * B
-    ref = np.convolve(x[:nchk], ir)[:nchk]
-    err = y[:nchk] - ref
-    parity = {"rms": float(np.sqrt(np.mean(err ** 2))), "max_abs": float(np.max(np.abs(err))),
-              "outputs_checked": int(nchk), "against": "exact float64 convolution (numpy) of the first blocks",
-              "tolerance_rms": 1e-7}
-    if parity["rms"] > 1e-7:
-        print(f"bench.py: PARITY FAILURE (config 2) {parity}", file=sys.stderr)
+    if dump:
+        dump_outputs(dump, {"y": y})
+    parity = None
+    if parity_on:
+        nchk = min(nblk, 4) * B
+        ref = np.convolve(x[:nchk], ir)[:nchk]
+        err = y[:nchk] - ref
+        parity = {"rms": float(np.sqrt(np.mean(err ** 2))), "max_abs": float(np.max(np.abs(err))),
+                  "outputs_checked": int(nchk), "against": "exact float64 convolution (numpy) of the first blocks",
+                  "tolerance_rms": 1e-7}
+        if parity["rms"] > 1e-7:
+            print(f"bench.py: PARITY FAILURE (config 2) {parity}", file=sys.stderr)
     cpu = None
     if cpu_leg:
         sys.path.insert(0, str(ROOT / "tests"))
@@ -881,7 +973,7 @@ def stream_measure(nblk: int, warmup_blocks: int, cpu_leg: bool) -> dict:
 def main_stream(args):
     """BASELINE config 2 as its own line (replicas only)."""
     nblk = max(1, args.samples // 4096) if args.samples else 2048
-    r = stream_measure(nblk, args.warmup * 8, not args.no_cpu_baseline)
+    r = stream_measure(nblk, args.warmup * 8, args.full and not args.no_cpu_baseline, args.full, args.dump_outputs)
     line = {
         "metric": "Msamples/sec, streaming overlap-save 16384-tap IR, 4096-sample blocks (config 2)",
         "value": r["value"], "unit": "Msamples/s", "n_gpus": 1, "steps": nblk,
@@ -910,11 +1002,13 @@ def _plan_radices(N):
     return [1 << (base + (1 if p < extra else 0)) for p in range(np_)]
 
 
-def corr_measure(steps: int, warmup: int, cpu_leg: bool, n: int | None = None, settle: int = 60) -> dict:
+def corr_measure(steps: int, warmup: int, cpu_leg: bool, n: int | None = None, settle: int = 60,
+                 parity_on: bool = True, dump=None) -> dict:
     """conv.CorrelateFFT (correlate.go:111-172) of two n-sample
     signals, one nextPow2(2n-1) = 2^24-point transform pair on the device
     (device-resident inputs/outputs; plans and work buffers cached), with the
-    parity of the measured output and the CPU leg.  Replicas only."""
+    parity of the measured output and the CPU leg.  Replicas only.  `dump`: a
+    --dump-outputs directory for the last timed call's result."""
     import ctypes as C
 
     import numpy as np
@@ -950,25 +1044,29 @@ def corr_measure(steps: int, warmup: int, cpu_leg: bool, n: int | None = None, s
     # parity of the measured output: 16-lag windows (result[j] = sum_i a[i + j - (n-1)] b[i],
     # correlate.go:176-185) at the most negative lags, around lag 0, two middles and the
     # most positive lags, against exact float64 dot products (numpy)
-    got = out.cpu().numpy()
-    wins = [0, n // 3, n - 1 - 8, n - 1 + n // 2, 2 * n - 2 - 15]
-    errs, refs = [], []
-    for j0 in wins:
-        for j in range(j0, j0 + 16):
-            lag = j - (n - 1)
-            ref = float(np.dot(ah[lag:], bh[:n - lag])) if lag >= 0 else float(np.dot(ah[:n + lag], bh[-lag:]))
-            errs.append(got[j] - ref)
-            refs.append(ref)
-    errs, refs = np.array(errs), np.array(refs)
-    scale = max(1.0, float(np.max(np.abs(refs))))
-    parity = {"max_abs": float(np.max(np.abs(errs))), "rms": float(np.sqrt(np.mean(errs ** 2))),
-              "max_rel": float(np.max(np.abs(errs)) / scale), "outputs_checked": int(errs.size),
-              "no_nan": bool(not np.isnan(got).any()),
-              "against": "exact float64 dot products (numpy) at lags " + ", ".join(str(j - (n - 1)) for j in wins) +
-                         " (+0..15)",
-              "tolerance": "max |err| <= 1e-10 max(1, max |ref|) (tests/test_spectral_gpu.py)"}
-    if not (parity["max_rel"] <= 1e-10 and parity["no_nan"]):
-        print(f"bench.py: CORRELATE PARITY FAILURE {parity}", file=sys.stderr)
+    if dump:
+        dump_outputs(dump, {"correlation": out})
+    parity = None
+    if parity_on:
+        got = out.cpu().numpy()
+        wins = [0, n // 3, n - 1 - 8, n - 1 + n // 2, 2 * n - 2 - 15]
+        errs, refs = [], []
+        for j0 in wins:
+            for j in range(j0, j0 + 16):
+                lag = j - (n - 1)
+                ref = float(np.dot(ah[lag:], bh[:n - lag])) if lag >= 0 else float(np.dot(ah[:n + lag], bh[-lag:]))
+                errs.append(got[j] - ref)
+                refs.append(ref)
+        errs, refs = np.array(errs), np.array(refs)
+        scale = max(1.0, float(np.max(np.abs(refs))))
+        parity = {"max_abs": float(np.max(np.abs(errs))), "rms": float(np.sqrt(np.mean(errs ** 2))),
+                  "max_rel": float(np.max(np.abs(errs)) / scale), "outputs_checked": int(errs.size),
+                  "no_nan": bool(not np.isnan(got).any()),
+                  "against": "exact float64 dot products (numpy) at lags " +
+                             ", ".join(str(j - (n - 1)) for j in wins) + " (+0..15)",
+                  "tolerance": "max |err| <= 1e-10 max(1, max |ref|) (tests/test_spectral_gpu.py)"}
+        if not (parity["max_rel"] <= 1e-10 and parity["no_nan"]):
+            print(f"bench.py: CORRELATE PARITY FAILURE {parity}", file=sys.stderr)
     N = 1 << (2 * n - 2).bit_length()
     # algorithmic bytes per call (DESIGN.md "spectral row") of the passes the
     # call runs: the forward transform of a + i b (its first pass reads the
@@ -1038,7 +1136,8 @@ def corr_measure(steps: int, warmup: int, cpu_leg: bool, n: int | None = None, s
 
 
 def main_corr(args):
-    r = corr_measure(args.steps, args.warmup, not args.no_cpu_baseline, args.samples, args.clock_settle)
+    r = corr_measure(args.steps, args.warmup, args.full and not args.no_cpu_baseline, args.samples, args.clock_settle,
+                     parity_on=args.full, dump=args.dump_outputs)
     line = {
         "metric": "Msamples/sec, CorrelateFFT of two 2^23-sample signals (input samples per second)",
         "value": r["value"], "unit": "Msamples/s", "n_gpus": 1, "steps": args.steps,
@@ -1109,13 +1208,16 @@ def fx_cpu_baseline(eq, comp_cfg, verb, fs, m):
                       f"({dt:.2f} s)"}
 
 
-def fx_measure(args, world, rank, local, dev, steps, warmup, cpu_leg, graph=None, n=None, parity_on=True) -> dict:
+def fx_measure(args, world, rank, local, dev, steps, warmup, cpu_leg, graph=None, n=None, parity_on=True,
+               dump=None) -> dict:
     """BASELINE config 5: effectchain filter(x5 RBJ) -> dyn-compressor ->
     reverb-freeverb on 256 channels x 2^20 samples (device buffers, the
     engine AUTO picks), `steps` timed calls after `warmup`; barrier +
     synchronize around them, max over ranks.  Parity: a fresh chain over the
     same input against the oracle chain on channels 0 and 255 (a 2^17-sample
-    prefix: the chain is causal)."""
+    prefix: the chain is causal).  `dump`: a --dump-outputs directory for the
+    buffer as the last timed call left it (the chain works in place and keeps
+    its state, so every call processes the previous call's output)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -1160,6 +1262,8 @@ def fx_measure(args, world, rank, local, dev, steps, warmup, cpu_leg, graph=None
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = world * C * n * steps / elapsed / 1e6
+    if dump and rank == 0:
+        dump_outputs(dump, {"y": x})
     engine = None
     if not graph:
         eng_id, noise = fx.LastEngine()
@@ -1224,8 +1328,8 @@ def main_fx(args):
     dev = torch.device("cuda", local)
     if world > 1:
         dist.init_process_group("nccl", device_id=dev)
-    r = fx_measure(args, world, rank, local, dev, args.steps, args.warmup, not args.no_cpu_baseline,
-                   graph=args.graph, n=args.samples)
+    r = fx_measure(args, world, rank, local, dev, args.steps, args.warmup, args.full and not args.no_cpu_baseline,
+                   graph=args.graph, n=args.samples, parity_on=args.full, dump=args.dump_outputs)
     if rank == 0:
         line = {
             "metric": "Msamples/sec, effectchain biquad EQ + Compressor + Freeverb (config 5)",

@@ -221,8 +221,10 @@ def _run_world(argv, world=2):
     return res
 
 
-BASE = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--clock-settle", "2", "--samples", "8192", "--no-cpu-baseline",
-        "--host-io", "off", "--shard-sub", "off", "--fx-leg", "off", "--stream-leg", "off"]
+PLAIN = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--clock-settle", "2", "--samples", "8192"]
+# --full: the parity, the per-kernel pass and the conv-only pass the assertions below read
+BASE = PLAIN + ["--full", "--no-cpu-baseline", "--host-io", "off", "--shard-sub", "off", "--fx-leg", "off",
+                "--stream-leg", "off"]
 
 
 @pytest.mark.parametrize("extra", [
@@ -256,6 +258,63 @@ def test_conv_main_world2_over_gloo(extra):
         steps_total = len(calls) // segs
         conv_only = 1 + min(3, 5)
         assert reduces == (steps_total - conv_only) * segs
+
+
+def test_conv_main_plain_run_world2_dumps_outputs(tmp_path):
+    """Without --full the run is the timed steps alone: settle + warm-up + steps,
+    every one with its reduce, nothing after them and no diagnostics in the
+    line.  --dump-outputs writes rank 0's reduced whole-job stereo mix of the
+    last timed step."""
+    from scipy.signal import fftconvolve
+
+    from algodsp import irlib, signals
+
+    res = _run_world(PLAIN + ["--dump-outputs", str(tmp_path / "out")])
+    assert {r: v[0] for r, v in res.items()} == {0: 0, 1: 0}
+    assert res[1][1] == "", "only rank 0 prints"
+    line = json.loads(res[0][1].strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line
+    assert line["steps"] == 3 and line["full"] is False
+    assert line["value"] == pytest.approx(2 * 8 * 8192 * 3 / (line["ms_per_step"] * 3e-3) / 1e6, rel=1e-3)
+    for key in ("parity", "roofline", "kernels", "mixdown_reduce", "cpu_baseline", "host_io", "config5"):
+        assert key not in line
+    for rank in (0, 1):
+        calls, reduces = res[rank][2], res[rank][3]
+        assert len(calls) == 2 + 1 + 3 and reduces == len(calls)
+    ir = irlib.large_church()
+    want = np.zeros((2, 8192 + ir.shape[1] - 1))
+    for c in range(16):
+        want[c % 2] += fftconvolve(signals.white_noise(8192, 0x5EED + c), ir[c % 2])
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["mix.npy"]
+    got = np.load(tmp_path / "out" / "mix.npy")
+    assert got.dtype == np.float64 and got.shape == want.shape
+    assert np.max(np.abs(got - want)) < 1e-9
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path):
+    """An output over the budget is written as the same seeded sample of its
+    columns on every call, both ends included, inside the budget."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    a = np.arange(3 * 100000, dtype=np.float64).reshape(3, 100000)
+    small = np.arange(10, dtype=np.float32)
+    budget = 1 << 20
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, {"big": torch.from_numpy(a), "small": small}, budget=budget)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["big.npy", "big_index.npy", "small.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= budget
+    big, idx = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "a" / "big_index.npy")
+    assert big.dtype == np.float64 and idx.dtype == np.float64
+    i = idx.astype(np.int64)
+    assert np.all(np.diff(i) > 0) and i[0] == 0 and i[-1] == 99999
+    assert set(range(bench.DUMP_EDGE)) <= set(i.tolist()) and i.size > 10000
+    assert np.array_equal(big, a[:, i])
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small.reshape(1, 10).astype(np.float64))
+    for n in names:
+        assert (tmp_path / "a" / n).read_bytes() == (tmp_path / "b" / n).read_bytes()
 
 
 def test_rank_mismatch_exits_before_any_gpu_call():

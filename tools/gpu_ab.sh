@@ -10,7 +10,7 @@ for v in ${VARIANTS:-"-"}; do
   i=$((i+1))
   envs=""
   [ "$v" != "-" ] && envs=${v//,/ }
-  env $envs timeout -k 10 200 python3 bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --host-io off \
+  env $envs timeout -k 10 200 python3 bench.py --steps ${STEPS:-20} --warmup 5 --full --no-cpu-baseline --host-io off \
       ${BENCH_ARGS:-} > gpurun_out/ab_$i.json 2> gpurun_out/ab_$i.err
   rc=$?
   if [ $rc -ne 0 ]; then echo "variant $v rc=$rc"; tail -5 gpurun_out/ab_$i.err; exit $rc; fi

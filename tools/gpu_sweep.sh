@@ -11,7 +11,7 @@ CFGS=${SWEEP:-"4096:0:128 8192:0:64"}
 for cfg in $CFGS; do
   IFS=: read hop chunk R envs <<< "$cfg"
   envs=${envs:-}
-  line=$(env AD_MAC_R=$R ${envs//,/ } timeout -k 10 200 python3 bench.py --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline \
+  line=$(env AD_MAC_R=$R ${envs//,/ } timeout -k 10 200 python3 bench.py --steps ${STEPS:-5} --warmup 2 --full --no-cpu-baseline \
          --kernel-timing off --hop $hop --chunk $chunk 2> gpurun_out/sweep_err.log)
   rc=$?
   if [ $rc -ne 0 ]; then echo "cfg $cfg rc=$rc"; tail -5 gpurun_out/sweep_err.log; exit $rc; fi

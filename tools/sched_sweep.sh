@@ -12,7 +12,7 @@ for v in ${SWEEP:-"serial pipelined:0:0"}; do
   IFS=: read -r mode chunk run <<< "$v"
   extra="--schedule $mode"
   [ "$mode" != "serial" ] && extra="$extra --pipe-chunk ${chunk:-0} --pipe-run ${run:-0}"
-  timeout -k 10 200 python3 bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --host-io off --shard-sub off \
+  timeout -k 10 200 python3 bench.py --steps ${STEPS:-20} --warmup 5 --full --no-cpu-baseline --host-io off --shard-sub off \
       $extra ${BENCH_ARGS:-} > gpurun_out/sweep_$i.json 2> gpurun_out/sweep_$i.err
   rc=$?
   if [ $rc -ne 0 ]; then echo "variant $v rc=$rc"; tail -5 gpurun_out/sweep_$i.err; exit $rc; fi
