@@ -1048,6 +1048,7 @@ int ad_conv_multi_create(const double* kernels, int n_ir, int64_t K, int64_t hop
     h->fft_size = 2 * hop;
     h->channels = channels;
     h->eng.reset(new Upols(dev, kernels, n_ir, K, (int)hop, channels, ir_index, (int)max_chunk_blocks, h->stream));
+    h->eng->set_single_tap_gain(true);  // K == 1: exact gain instead of an FFT round trip
     return h.release();
   });
 }
@@ -1092,6 +1093,18 @@ int ad_conv_multi_get_schedule(const ad_conv* h, int* mode, int64_t* chunk_block
   });
 }
 
+namespace {
+// The row contract of the multi-channel device calls (include/algodsp.h,
+// "Device buffers"): non-null pointers, and with more than one channel a row
+// stride that holds the row.  Checked before any device work.
+void check_multi_rows(const ad_conv* h, const double* d_in, int64_t in_stride, int64_t in_len, const double* d_out,
+                      int64_t out_stride, int64_t out_len) {
+  if (!d_in || !d_out) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null device buffer");
+  if (h->channels > 1 && (in_stride < in_len || out_stride < out_len))
+    AD_FAIL(AD_ERR_LENGTH_MISMATCH, "conv: stride shorter than the row");
+}
+}  // namespace
+
 int ad_conv_multi_process_device(ad_conv* h, const double* d_in, int64_t in_stride, int64_t in_len, double* d_out,
                                  int64_t out_stride, int64_t out_len, void* stream) {
   return guard([&] {
@@ -1099,6 +1112,7 @@ int ad_conv_multi_process_device(ad_conv* h, const double* d_in, int64_t in_stri
     if (in_len <= 0) AD_FAIL(AD_ERR_EMPTY_INPUT, "conv: empty input");
     if (out_len > in_len + h->K - 1 || out_len <= 0)
       AD_FAIL(AD_ERR_LENGTH_MISMATCH, "conv: buffer length mismatch");
+    check_multi_rows(h, d_in, in_stride, in_len, d_out, out_stride, out_len);
     DeviceScope ds(h->device);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);  // NULL = the default (null) stream
     order_after_last(h, s);
@@ -1118,6 +1132,7 @@ int ad_conv_multi_process_device_segment(ad_conv* h, const double* d_in, int64_t
     if (in_len <= 0) AD_FAIL(AD_ERR_EMPTY_INPUT, "conv: empty input");
     if (out_len > in_len + h->K - 1 || out_len <= 0)
       AD_FAIL(AD_ERR_LENGTH_MISMATCH, "conv: buffer length mismatch");
+    check_multi_rows(h, d_in, in_stride, in_len, d_out, out_stride, out_len);
     const int64_t L = h->eng->hop();
     out_end = std::min(out_end, out_len);
     if (out_begin < 0 || out_begin >= out_end || out_begin % L != 0 || (out_end % L != 0 && out_end != out_len))
@@ -1144,6 +1159,7 @@ int ad_conv_multi_process_device_mix(ad_conv* h, const double* d_in, int64_t in_
     if (in_len <= 0) AD_FAIL(AD_ERR_EMPTY_INPUT, "conv: empty input");
     if (out_len > in_len + h->K - 1 || out_len <= 0)
       AD_FAIL(AD_ERR_LENGTH_MISMATCH, "conv: buffer length mismatch");
+    check_multi_rows(h, d_in, in_stride, in_len, d_mix, mix_stride, out_len);
     if (!d_mix) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "mixdown: null mix buffer");
     if (mix_stride < out_len) AD_FAIL(AD_ERR_LENGTH_MISMATCH, "mixdown: mix stride shorter than the output");
     const int64_t L = h->eng->hop();

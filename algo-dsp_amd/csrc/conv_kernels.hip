@@ -743,6 +743,32 @@ __global__ __launch_bounds__(256) void k_mixdown(const double* __restrict__ ch, 
   mix[mix_stride + t] = first_parity ? e : o;
 }
 
+// A one-tap impulse response (K == 1): the convolution is a gain, so the
+// many-channel engine skips its transforms (Upols::run) and the result is the
+// reference's own arithmetic, 0 + h[0] x[t] rounded once (conv.Direct's
+// scatter-add into a zeroed dst, conv.go:97-154), not an FFT round trip's.
+// y[c][t] for t in [t0, t1): inputs at or past n read as zeros.  Mix form
+// (grid.y = 2 sides): y is the [2][y_stride] stereo mix, each side the sum of
+// its channels in increasing c, as k_mixdown sums them.
+__global__ __launch_bounds__(256) void k_single_tap(SingleTapArgs a) {
+#pragma clang fp contract(off)
+  const int64_t t = a.t0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.t1) return;
+  if (a.mix) {
+    const int side = blockIdx.y;
+    double acc = 0.0;
+    if (t < a.n)
+      for (int c = (side ^ a.mix_parity) & 1; c < a.channels; c += 2)
+        acc += 0.0 + a.taps[a.ir_index[c]] * a.x[(int64_t)c * a.x_stride + t];
+    a.y[(int64_t)side * a.y_stride + t] = acc;
+    return;
+  }
+  const int c = blockIdx.y;
+  const double v = t < a.n ? 0.0 + a.taps[a.ir_index[c]] * a.x[(int64_t)c * a.x_stride + t] : 0.0;
+  double* y = a.y + (int64_t)c * a.y_stride + t;
+  *y = a.accumulate ? *y + v : v;
+}
+
 // Column shift with zero fill (accumulator / FIFO compaction of the
 // multichannel partitioned engine).
 __global__ __launch_bounds__(256) void k_shift_cols(const double* __restrict__ src, int64_t src_stride,
@@ -970,6 +996,12 @@ void launch_mixdown(const double* ch, int channels, int64_t stride, int64_t len,
                     int first_parity, hipStream_t s) {
   hipLaunchKernelGGL(k_mixdown, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, ch, channels, stride, len, mix,
                      mix_stride, first_parity & 1);
+}
+
+void launch_single_tap(const SingleTapArgs& a, hipStream_t s) {
+  if (a.channels <= 0 || a.t1 <= a.t0) return;
+  hipLaunchKernelGGL(k_single_tap, dim3((unsigned)((a.t1 - a.t0 + 255) / 256), (unsigned)(a.mix ? 2 : a.channels)),
+                     dim3(256), 0, s, a);
 }
 
 void launch_shift_cols(const double* src, int64_t src_stride, double* dst, int64_t dst_stride, int channels,

@@ -190,6 +190,19 @@ void launch_direct_circular(const double* a, const double* b, int64_t n, double*
 void launch_stream_direct(const double* h, int64_t K, const double* buf, int64_t B, double* y, hipStream_t s);
 void launch_mixdown(const double* ch, int channels, int64_t stride, int64_t len, double* mix, int64_t mix_stride,
                     int first_parity, hipStream_t s);
+// The one-tap engine path (k_single_tap): y[c][t] = 0 + taps[ir_index[c]] * x[c][t]
+// for t in [t0, t1), zeros from x at or past n; accumulate adds into y; mix
+// writes the [2][y_stride] stereo mix of the channels instead.
+struct SingleTapArgs {
+  const double* x;
+  int64_t x_stride, n;
+  double* y;
+  int64_t y_stride, t0, t1;
+  const double* taps;    // [n_ir]
+  const int* ir_index;   // [channels]
+  int channels, accumulate, mix, mix_parity;
+};
+void launch_single_tap(const SingleTapArgs& a, hipStream_t s);
 // One small partitioned stage (two partitions of p <= 1024 taps) for nb
 // consecutive blocks of every channel, fused and stateless: a workgroup per
 // (block, channel) transforms both input windows x[d-2p, d) and x[d-p, d+p)

@@ -91,6 +91,10 @@ Upols::Upols(int device, const double* kernels, int n_ir, int64_t K, int L, int 
     if (irm[c] < 0 || irm[c] >= n_ir_) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "ir_index out of range");
   irmap_.alloc(C_);
   AD_HIP(hipMemcpyAsync(irmap_.p, irm.data(), C_ * sizeof(int), hipMemcpyHostToDevice, stream_));
+  if (K_ == 1) {  // kernels is [n_ir][1]
+    tap0_.alloc((size_t)n_ir_);
+    AD_HIP(hipMemcpyAsync(tap0_.p, kernels, (size_t)n_ir_ * sizeof(double), hipMemcpyHostToDevice, stream_));
+  }
   reset_stream(stream_);
   // dparts must outlive the K1 launch that reads it
   AD_HIP(hipStreamSynchronize(stream_));
@@ -350,6 +354,26 @@ void Upols::run(const double* d_in, int64_t in_stride, int64_t n, double* d_out,
   if (je < 0) je = (out_len + L_ - 1) / L_;
   const int64_t J = je - jb;
   if (J <= 0) return;
+  if (single_tap_ && !gate_on_) {  // a gain: no transforms, no delay line (set_single_tap_gain)
+    SingleTapArgs a{};
+    a.x = d_in;
+    a.x_stride = in_stride;
+    a.n = n;
+    a.y = mix ? mix->p : d_out;
+    a.y_stride = mix ? mix->stride : out_stride;
+    a.t0 = jb * L_;
+    a.t1 = std::min<int64_t>(je * L_, out_len);
+    a.taps = tap0_.p;
+    a.ir_index = irmap_.p;
+    a.channels = C_;
+    a.accumulate = accumulate ? 1 : 0;
+    a.mix = mix ? 1 : 0;
+    a.mix_parity = mix ? (mix->first_parity & 1) : 0;
+    launch_single_tap(a, s);
+    AD_HIP(hipGetLastError());
+    g_next_ += J;
+    return;
+  }
   Io io{};
   io.in = d_in;
   io.in_stride = in_stride;

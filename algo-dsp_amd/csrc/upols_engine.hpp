@@ -69,6 +69,11 @@ class Upols {
            bool use_hist, hipStream_t s, int64_t jb = 0, int64_t je = -1, bool accumulate = false,
            const MixOut* mix = nullptr);
   bool can_mix() const { return M_ >= 2048; }
+  // K == 1 only: run() computes y = 0 + h[0] x in one kernel instead of the
+  // transforms (a one-tap convolution is a gain; the result is then exact).
+  // The offline many-channel handle opts in; every run of a handle takes the
+  // same path, so its calls, segments and mixes stay bit-consistent.
+  void set_single_tap_gain(bool on) { single_tap_ = on && K_ == 1; }
 
   // Offline schedule of the device entry points (ad_conv_multi_set_schedule).
   // SERIAL: each chunk's K1 -> K2 -> K3 on the caller's stream, chunks of up
@@ -115,6 +120,8 @@ class Upols {
   DevBuf<double2> X_;    // [C][Q][MS]
   DevBuf<double2> Y_;    // [C][jc_max][MS]
   DevBuf<int> irmap_;    // [C]
+  DevBuf<double> tap0_;  // [n_ir] the taps of one-tap IRs (K == 1)
+  bool single_tap_ = false;
 
   // One chunk of output blocks and the buffers its kernels use.
   struct Chunk {

@@ -16,6 +16,27 @@
  *    retaining Go pointers); `*_device` calls take device pointers and a HIP
  *    stream (`void*`, NULL = the HIP default stream, as in the HIP API) and are
  *    asynchronous with respect to the host;
+ *  - Device buffers.  Every `*_device` call takes rows of `len` elements at a
+ *    row stride counted in elements ([channels][stride]; a one-shot call's
+ *    array is one row).  For all of them:
+ *    1. alignment: any 8-byte-aligned double* (2-byte-aligned uint16_t* for
+ *       ad_decode_f16_device) and any stride >= the row length are accepted;
+ *       16-byte alignment and even strides are faster, never required;
+ *    2. extent: a buffer of C rows is (C-1)*stride + len elements, not
+ *       C*stride -- nothing after the last row's len elements is touched;
+ *    3. reads: only [c*stride, c*stride + len) of each input row is read, no
+ *       other element can influence a result, and an out-of-place call leaves
+ *       its input bit-unchanged;
+ *    4. writes: only the documented output range of each row is written --
+ *       out_len elements, [out_begin, min(out_end, out_len)) for the segment
+ *       and mix calls, n elements for the in-place calls; every other byte of
+ *       the caller's (the padding between rows, the memory before the base
+ *       and after the last row) keeps its bits;
+ *    5. layout independence: for a fixed handle configuration and fixed
+ *       lengths the results do not depend on base alignment or strides; they
+ *       are bit-identical to the contiguous, 16-byte-aligned call.
+ *    Input and output may be the same buffer only where a call says so (the
+ *    in-place calls; ad_fir_process_device with d_dst == d_src).
  *  - a handle is single-caller, like the reference types (no internal locks);
  *  - ad_last_error() returns a thread-local description of the last failure.
  *  - there is no CPU fallback: with no usable GPU the create calls fail with
@@ -182,7 +203,9 @@ int ad_conv_convolve(const double* a, int64_t n, const double* b, int64_t m, int
  * hop: partition/hop length (power of two, 64..8192); 0 = auto (min(8192, nextpow2(max(K, 256))).
  * channels: number of channels processed per call; ir_index[c] selects the
  *   IR of channel c (NULL: c % n_ir).
- * max_chunk_blocks: blocks per channel per internal chunk (0 = auto).     */
+ * max_chunk_blocks: blocks per channel per internal chunk (0 = auto).
+ * kernel_len == 1 is a gain: every call of the handle (device, segment, mix,
+ * host) computes 0 + h[0] x[t] in one kernel, bit-exact with conv.Direct.  */
 int ad_conv_multi_create(const double* kernels, int n_ir, int64_t kernel_len, int64_t hop, int channels,
                          const int32_t* ir_index, int64_t max_chunk_blocks, int device, ad_conv** out);
 /* Offline schedule of the device calls below (no reference counterpart: how
@@ -204,7 +227,11 @@ int ad_conv_multi_get_schedule(const ad_conv* h, int* mode, int64_t* chunk_block
 /* Full linear convolution of every channel (ModeFull semantics per channel):
  * d_in  [channels][in_stride] (first in_len used),
  * d_out [channels][out_stride] (first out_len written; out_len <= in_len+K-1).
- * Device pointers; asynchronous on `stream` (NULL = default stream).      */
+ * Device pointers; asynchronous on `stream` (NULL = default stream).
+ * This call and the segment and mix forms below check the rows before any
+ * device work: a null d_in / d_out / d_mix -> AD_ERR_INVALID_ARGUMENT; with
+ * more than one channel, in_stride < in_len or out_stride < out_len (the mix
+ * form: mix_stride < out_len, for any channel count) -> AD_ERR_LENGTH_MISMATCH. */
 int ad_conv_multi_process_device(ad_conv* h, const double* d_in, int64_t in_stride, int64_t in_len, double* d_out,
                                  int64_t out_stride, int64_t out_len, void* stream);
 /* The same full linear convolution computed one output segment at a time:
