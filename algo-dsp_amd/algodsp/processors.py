@@ -190,8 +190,17 @@ class Compressor(_FxChain):
     def SetAutoMakeup(self, on: bool):
         self._set(auto_makeup=int(bool(on)))
 
-    def SetMakeupGain(self, db):
-        self._set(makeup_db=db)
+    def SetMakeupGain(self, db):  # SetManualMakeupGain (core.go:201-210) turns auto makeup off
+        self._set(makeup_db=db, auto_makeup=0)
+
+    def SetTopology(self, topology: int):  # core.go:106-114
+        self._set(topology=int(topology))
+
+    def SetDetectorMode(self, mode: int):  # core.go:116-124
+        self._set(detector_mode=int(mode))
+
+    def SetFeedbackRatioScale(self, on: bool):  # core.go:126-129
+        self._set(feedback_ratio_scale=int(bool(on)))
 
     def ProcessInPlace(self, buf):  # compressor.go:362-366
         self._process(buf)

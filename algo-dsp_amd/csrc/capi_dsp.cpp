@@ -218,6 +218,46 @@ void fx_reset_comp(ad_fx_chain* h) {
   AD_HIP(hipMemsetAsync(h->ring.p, 0, h->ring.n * sizeof(double), h->stream));
 }
 
+// New dynamics parameters on a quiesced handle, with the reference setters'
+// effect on the state (core.go:186-250, 500-518, 606-650): the first
+// configuration starts from Reset; later ones keep the envelope, the
+// feedback memory, the metrics and the gate's hold counter.  A changed RMS
+// window length restarts the ring alone (fresh zeroed ring, index, fill and
+// sum, in either detector mode), and a side-chain cut turned off zeroes that
+// one-pole's state, so turning it on again starts from zero.
+void fx_set_comp_params(ad_fx_chain* h, const CompParams& p) {
+  const bool first = !h->comp_on;
+  const bool ring_new = !first && p.rms_n != h->cp.rms_n;
+  const bool lp_off = !first && h->cp.lp_on && !p.lp_on;
+  const bool hp_off = !first && h->cp.hp_on && !p.hp_on;
+  h->cp = p;
+  h->comp_on = true;
+  if (first) {
+    h->cs.alloc((size_t)h->channels);
+    h->ring.alloc((size_t)h->channels * p.rms_n);
+    fx_reset_comp(h);
+    fx_quiesce(h);
+    return;
+  }
+  if (!ring_new && !lp_off && !hp_off) return;
+  std::vector<CompChState> st(h->channels);
+  AD_HIP(hipMemcpy(st.data(), h->cs.p, st.size() * sizeof(CompChState), hipMemcpyDeviceToHost));
+  for (auto& s : st) {
+    if (ring_new) {
+      s.rms_index = 0;
+      s.rms_filled = 0;
+      s.rms_sum = 0.0;
+    }
+    if (lp_off) s.lp = 0.0;
+    if (hp_off) s.hp = 0.0;
+  }
+  if (ring_new) {
+    h->ring.alloc((size_t)h->channels * p.rms_n);
+    AD_HIP(hipMemset(h->ring.p, 0, h->ring.n * sizeof(double)));
+  }
+  AD_HIP(hipMemcpy(h->cs.p, st.data(), st.size() * sizeof(CompChState), hipMemcpyHostToDevice));
+}
+
 void fx_reset_verb(ad_fx_chain* h) {
   if (!h->verb_on) return;
   AD_HIP(hipMemsetAsync(h->vs.p, 0, h->vs.n * sizeof(VerbChState), h->stream));
@@ -1067,16 +1107,7 @@ int ad_fx_chain_set_compressor(ad_fx_chain* h, const ad_compressor_config* cfg) 
       return;
     }
     check_comp_config(*cfg);
-    const CompParams p = comp_params(*cfg);
-    const bool fresh = !h->comp_on || p.rms_n != h->cp.rms_n;
-    h->cp = p;
-    h->comp_on = true;
-    if (fresh) {
-      h->cs.alloc((size_t)h->channels);
-      h->ring.alloc((size_t)h->channels * p.rms_n);
-      fx_reset_comp(h);
-      fx_quiesce(h);
-    }
+    fx_set_comp_params(h, comp_params(*cfg));
   });
 }
 
@@ -1106,15 +1137,7 @@ int ad_fx_chain_set_expander(ad_fx_chain* h, const ad_compressor_config* cfg, in
     p.ratio_m1 = g.ratio - 1.0;
     p.range_lin = std::pow(10.0, range_db / 20.0);
     p.hold_n = gate ? (int)(hold_ms * 0.001 * g.sample_rate) : 0;
-    const bool fresh = !h->comp_on || p.rms_n != h->cp.rms_n;
-    h->cp = p;
-    h->comp_on = true;
-    if (fresh) {
-      h->cs.alloc((size_t)h->channels);
-      h->ring.alloc((size_t)h->channels * p.rms_n);
-      fx_reset_comp(h);
-      fx_quiesce(h);
-    }
+    fx_set_comp_params(h, p);
   });
 }
 

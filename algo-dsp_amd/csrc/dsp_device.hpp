@@ -15,8 +15,12 @@ namespace adsp {
 // the step is env + c1 (src - env) + c2 |src - env|, written as
 //   fma(c2, |src - env|, fma(1 - c1, env, c1 src))
 // with c1 = (attack + b)/2, c2 = (attack - b)/2 (CompParams::env_*).  The map
-// is the reference's; the rounding is not (a few ulps on the envelope, which
-// the gain's log2 / exp2 already make a tolerance).  The
+// is the reference's; the rounding is not: a few ulps per step, and a bias from
+// the rounded k1 = 1 - c1 (up to 2^-54 per step relative, so up to
+// 2^-54 / (1 - pole) on a settled envelope: 8e-13 at a 100 ms release and
+// 48 kHz), which the gain's log2 / exp2 already make a tolerance.
+// The feedback topology, whose ratio-scaled poles and slope amplify that bias
+// past the 1e-12 bar, uses the reference's operations instead (k_chain).  The
 // reference's form is a compare, a select and three dependent operations on
 // the envelope, 109 clocks per sample for one wave on gfx950; this one has no
 // compare or select (|.| is a source modifier) and two dependent FMAs: 24.5

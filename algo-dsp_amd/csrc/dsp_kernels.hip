@@ -147,7 +147,18 @@ __global__ __launch_bounds__(64) void k_chain(ChainArgs a) {
           const double mean = cs.rms_sum / (double)p.rms_n;
           src = mean <= 0.0 ? 0.0 : sqrt(mean);
         }
-        cs.env = env_step(p, cs.env, src);
+        if (p.topology_fb) {
+          // The feedback loop (gain -> output -> detector) has log2 / exp2 in
+          // it, so the envelope step is not its floor: the reference's own
+          // operations (core.go:351-355).  env_step's rounded k1 = 1 - c1
+          // biases the envelope by up to 2^-54 / (1 - pole) relative, which
+          // the ratio-scaled time constants (poles within 1e-6 of 1) and the
+          // ratio-scaled slope (cf up to 99) of this topology turn into 4e-11
+          // on the output (ratio 100, knee 0, 44.1 kHz, 2500 samples).
+          cs.env = src > cs.env ? cs.env + (src - cs.env) * p.attack : src + (cs.env - src) * p.release;
+        } else {
+          cs.env = env_step(p, cs.env, src);
+        }
         double g = gain_for_level(p, cs.env);
         if (p.mode == 2) {  // gate hold (gate.go:361-366)
           if (g >= 1.0) {

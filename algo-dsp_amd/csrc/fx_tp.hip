@@ -30,8 +30,11 @@
 //          geometrically (da = damp < 1).  Such a piece is cut into up to 16
 //          lane segments; segment w > 0 starts its filter `wu` samples early
 //          from zero (da^wu < 2^-60: by its first output the run has met the
-//          serial value, to the last bit in every case tested), segment 0
-//          continues the exact carried value.  Every allpass delay is >= 225
+//          serial value, nearly always to the last bit; the kernel checks each
+//          segment's start against the end of the one before and lets a
+//          segment that is off run again from the right value until it meets
+//          the run it made: comb_piece_settle), segment 0 continues the exact
+//          carried value.  Every allpass delay is >= 225
 //          samples, so the 225 samples of a window are independent.  One
 //          channel per workgroup with all its delay lines in LDS.
 #include <hip/hip_runtime.h>
@@ -638,6 +641,54 @@ __device__ __forceinline__ double comb_fs(const VerbParams& p, double out, doubl
   return f;
 }
 
+// The lane segments of a comb piece are the serial recurrence exactly when
+// every warm-started segment begins on the value the segment before it ended
+// on (segment 0 begins on the carried one, so by induction all are exact).
+// The warm-up gets there when its zero start is forgotten, to the last bit,
+// by the segment's first sample.  It is not when the filter value is near
+// zero there (few bits above the remnant: about 0.3 % of the segments, off by
+// an ulp or a few), behind a level drop of more than 2^60 (a 1e200 sample),
+// or where the flush to zero acts on one run and not the other.  Such a
+// segment runs again from the right start beside the run it made (`o8`: its
+// first line values, kept in registers) until the two meet, after which
+// everything it stored stands: a step or two for a last-bit difference.  One
+// that has not met after 8 samples runs to its end (the line values from the
+// comb outputs it stored itself).  Then the starts are compared again:
+// segment k is final after k rounds at most.
+__device__ __forceinline__ void comb_piece_settle(const VerbParams& p, double* L, const double* co, const double* xs,
+                                                  int s0, int s1, bool warm, double fs0, const double (&o8)[8],
+                                                  double& fs) {
+#pragma clang fp contract(off)
+  for (int round = 0; round < kVbSeg; ++round) {
+    const double prev_end = __shfl_up(fs, 1);
+    const bool off = warm && __double_as_longlong(fs0) != __double_as_longlong(prev_end);
+    if (__builtin_amdgcn_ballot_w64(off) == 0) break;
+    if (off) {
+      double fn = prev_end, fo = fs0;
+      fs0 = prev_end;
+      bool met = false;
+      int j = s0;
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        if (!met && j < s1) {
+          fn = comb_fs(p, o8[t], fn);
+          fo = comb_fs(p, o8[t], fo);
+          L[j] = p.gain * xs[j] + fn * p.feedback;
+          met = __double_as_longlong(fn) == __double_as_longlong(fo);
+          ++j;
+        }
+      }
+      if (!met) {
+        for (; j < s1; ++j) {
+          fn = comb_fs(p, co[j], fn);
+          L[j] = p.gain * xs[j] + fn * p.feedback;
+        }
+        fs = fn;
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(kVbThreads) void k_fxtp_verb(FxStageArgs a, const double* __restrict__ xC, int64_t xstride,
                                                           double* __restrict__ vbufC, double* __restrict__ coC,
                                                           int wu) {
@@ -714,6 +765,10 @@ __global__ __launch_bounds__(kVbThreads) void k_fxtp_verb(FxStageArgs a, const d
           }
           for (; j < s0; ++j) fs = comb_fs(p, L[pos0 + j], fs);
         }
+        const double fs0 = fs;  // the segment's start value
+        double o8[8];           // its first line values (comb_piece_settle)
+#pragma unroll
+        for (int t = 0; t < 8; ++t) o8[t] = mine && nw > 1 ? L[pos0 + min(s0 + t, s1 - 1)] : 0.0;
         if (mine) {
           int j = s0;
           for (; j + 8 <= s1; j += 8) {
@@ -738,6 +793,7 @@ __global__ __launch_bounds__(kVbThreads) void k_fxtp_verb(FxStageArgs a, const d
             cw[r + j] = out;
           }
         }
+        comb_piece_settle(p, L + pos0, cw + r, xs + r, s0, s1, mine && l > 0 && wu > 0, fs0, o8, fs);
         const int lastl = (m - 1) / Lw;
         carry = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(fs), lastl),
                                  __builtin_amdgcn_readlane(__double2loint(fs), lastl));
@@ -884,6 +940,10 @@ __global__ __launch_bounds__(kVbThreads) void k_fxtp_verb_pipe(FxStageArgs a, co
             }
             for (; j < s0; ++j) fs = comb_fs(p, L[pos0 + j], fs);
           }
+          const double fs0 = fs;  // the segment's start value
+          double o8[8];           // its first line values (comb_piece_settle)
+#pragma unroll
+          for (int t = 0; t < 8; ++t) o8[t] = mine && nw > 1 ? L[pos0 + min(s0 + t, s1 - 1)] : 0.0;
           if (mine) {
             int j = s0;
             for (; j + 8 <= s1; j += 8) {
@@ -908,6 +968,7 @@ __global__ __launch_bounds__(kVbThreads) void k_fxtp_verb_pipe(FxStageArgs a, co
               cw[r + j] = out;
             }
           }
+          comb_piece_settle(p, L + pos0, cw + r, xs + r, s0, s1, mine && l > 0 && wu > 0, fs0, o8, fs);
           const int lastl = (m - 1) / Lw;
           carry = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(fs), lastl),
                                    __builtin_amdgcn_readlane(__double2loint(fs), lastl));

@@ -394,6 +394,19 @@ typedef struct ad_compressor_config {
   int feedback_ratio_scale; /* 1: feedback topology scales time constants and ratio */
   int auto_makeup;          /* 1: makeup = -threshold*(1-1/ratio) */
 } ad_compressor_config;
+/* Non-finite detector levels (an Inf or NaN sample, or a square that overflows
+ * in the RMS detector).  The envelope follower computes the reference's map
+ * env + k (src - env), k = attack or 1 - release, as two FMAs with
+ * c2 = (attack - (1 - release)) / 2 (csrc/dsp_device.hpp env_step).  With
+ * c2 > 0 (the attack coefficient above 1 - release coefficient: any attack
+ * faster than the release) it gives the reference's result on a non-finite
+ * level too: the same NaN samples and the same exact zeros afterwards.  With
+ * c2 <= 0 (an attack as slow as the release, or slower) an infinite level
+ * makes the envelope Inf - Inf = NaN, and the output is NaN from that sample
+ * until Reset(), where the reference's envelope stays +Inf and its output is
+ * exact zeros.  The deviation is kept: the select that would remove it sits on
+ * the two-FMA envelope chain, the chain's longest recurrence.
+ * Channels are independent: a poisoned channel never changes another one. */
 /* NewCompressor(sampleRate) defaults (compressor.go:77-127). */
 void ad_compressor_default_config(ad_compressor_config* cfg, double sample_rate);
 /* The setters' validation of a whole config, host only (no device needed):
@@ -414,6 +427,12 @@ int ad_fx_chain_set_eq(ad_fx_chain* h, const double* sections, int nsec, int per
  * a section is unstable: |a2| >= 1 or |a1| >= 1 + a2).  Host only, no device
  * needed; no reference counterpart (diagnostics).                         */
 int ad_fx_eq_noise(const double* sections, int nsec, int sets, double* noise);
+/* The first configuration of the dynamics stage starts it from Reset().  A
+ * later call is the reference's setters (core.go:101-250): the envelope, the
+ * feedback memory, the metrics and the gate's hold counter carry on; a changed
+ * RMS window length (in samples) restarts the RMS ring, index, fill and sum
+ * only, in either detector mode (core.go:500-518); a side-chain cut set to 0
+ * zeroes that filter's state (core.go:606-650). */
 int ad_fx_chain_set_compressor(ad_fx_chain* h, const ad_compressor_config* cfg); /* NULL: stage off */
 /* dynamics.Expander / dynamics.Gate (expander.go, gate.go) as the chain's
  * dynamics stage instead of the compressor: cfg gives threshold, ratio, knee,

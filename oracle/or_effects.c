@@ -58,6 +58,7 @@ struct or_comp {
   double m_in_peak, m_out_peak, m_gr;
   int mode;              /* 0 compressor, 1 expander, 2 gate */
   double range_lin;      /* expander/gate floor (mathPower10(rangeDB/20)) */
+  double hold_ms;        /* gate: holdMs as set (SetSampleRate re-derives hold_samples) */
   int64_t hold_samples;  /* gate: int(holdMs * 0.001 * fs) */
   int64_t hold_counter;
 };
@@ -188,19 +189,46 @@ double or_comp_gain_for_level(const or_comp* c, double level) {
   return c->mode ? expansion_gain(c, level) : gain_for_level(c, level);
 }
 
-void or_comp_set_expander(or_comp* c, int mode, double range_db, double hold_ms) {
-  /* NewExpander / NewGate: core with autoMakeup off, makeup 0 dB
-   * (expander.go:88-104, gate.go:106-122); the feedback-scaled time
-   * constants are not enabled by these constructors */
-  c->mode = mode;
+/* The expander/gate core: autoMakeup off, makeup 0 dB (expander.go:88-104,
+ * gate.go:106-122); the feedback-scaled time constants are not enabled by
+ * these constructors */
+static void expander_core_cfg(or_comp* c) {
   c->cfg.auto_makeup = 0;
   c->cfg.makeup_db = 0.0;
   c->cfg.feedback_ratio_scale = 0;
+}
+
+void or_comp_set_expander(or_comp* c, int mode, double range_db, double hold_ms) {
+  /* NewExpander / NewGate, and mid-stream SetRange (updateCoefficients,
+   * gate.go:225-234) / SetHold (updateTimeConstants, gate.go:196-205,
+   * 419-422): both re-derive a parameter only; the hold counter is touched
+   * by ProcessSample and Reset alone (gate.go:361-366, 394-399) */
+  c->mode = mode;
+  expander_core_cfg(c);
   comp_recalc(c);
   c->range_lin = pow(10.0, range_db / 20.0);
+  c->hold_ms = hold_ms;
   c->hold_samples = mode == 2 ? (int64_t)(hold_ms * 0.001 * c->cfg.sample_rate) : 0;
-  c->hold_counter = 0;
 }
+
+void or_comp_set_cfg(or_comp* c, const or_comp_cfg* cfg) {
+  /* Every dynamicsCore setter (core.go:101-250) stores its field and runs one
+   * of recalculateDetectorCoefficients / recalculateRMSBuffer /
+   * recalculateGainComputer / recalculatePrefilter (core.go:480-570), each a
+   * pure function of the config except: the RMS ring, its index, fill and sum
+   * are cleared when (only when) the window's sample count changes, and a
+   * side-chain cut set to 0 zeroes that one-pole's state (Configure,
+   * core.go:606-617, 638-650).  comp_recalc is all four, so replacing the
+   * config and running it equals any sequence of setters that ends in `cfg`.
+   * The envelope, previousGain, previousAbsSample, the metrics and the gate's
+   * hold counter are not touched by any setter. */
+  c->cfg = *cfg;
+  if (c->mode) expander_core_cfg(c);
+  comp_recalc(c);
+  if (c->mode == 2) c->hold_samples = (int64_t)(c->hold_ms * 0.001 * c->cfg.sample_rate);
+}
+
+void or_comp_get_cfg(const or_comp* c, or_comp_cfg* cfg) { *cfg = c->cfg; }
 
 int or_comp_hold_counter(const or_comp* c) { return (int)c->hold_counter; }
 

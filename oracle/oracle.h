@@ -156,8 +156,15 @@ void or_comp_free(or_comp* c);
 /* dynamics.Expander / dynamics.Gate (expander.go, gate.go): the same detector
  * core with the downward-expansion gain (expander.go:358-411), no makeup,
  * range floor; the gate adds a hold counter (gate.go:354-375).
- * mode 1 = expander, 2 = gate.  Resets the hold counter. */
+ * mode 1 = expander, 2 = gate.  Also SetRange / SetHold mid-stream: the hold
+ * counter (zero after or_comp_new / or_comp_reset) is kept. */
 void or_comp_set_expander(or_comp* c, int mode, double range_db, double hold_ms);
+/* Re-configuration with the reference setters' semantics (core.go:101-250):
+ * replaces the config and re-derives the parameters.  State survives, except
+ * that the RMS ring restarts when its length changes and a side-chain cut set
+ * to 0 zeroes that filter's state. */
+void or_comp_set_cfg(or_comp* c, const or_comp_cfg* cfg);
+void or_comp_get_cfg(const or_comp* c, or_comp_cfg* cfg);
 int or_comp_hold_counter(const or_comp* c);
 double or_comp_gain_for_level(const or_comp* c, double level);
 

@@ -95,6 +95,8 @@ def lib() -> C.CDLL:
             "or_comp_params": (None, [vp, dp, dp, dp, dp, dp]),
             "or_comp_free": (None, [vp]),
             "or_comp_set_expander": (None, [vp, C.c_int, C.c_double, C.c_double]),
+            "or_comp_set_cfg": (None, [vp, vp]),
+            "or_comp_get_cfg": (None, [vp, vp]),
             "or_comp_hold_counter": (C.c_int, [vp]),
             "or_comp_gain_for_level": (C.c_double, [vp, C.c_double]),
             "or_verb_new": (vp, []),
@@ -434,6 +436,25 @@ class Compressor:
     def reset(self):
         lib().or_comp_reset(self.h)
 
+    def reconfigure(self, **kw):
+        """The reference's setters mid-stream (core.go:101-250): the fields in
+        `kw` replace the config's, everything derived is recomputed, the state
+        carries on (or_comp_set_cfg)."""
+        for k, v in kw.items():
+            setattr(self.cfg, k, v)
+        lib().or_comp_set_cfg(self.h, C.byref(self.cfg))
+
+    def set_makeup_gain(self, db):
+        """SetMakeupGain -> SetManualMakeupGain (core.go:201-210): also turns
+        auto makeup off."""
+        self.reconfigure(makeup_db=float(db), auto_makeup=0)
+
+    def config(self):
+        """The config the core holds now (the reference's getters)."""
+        g = CompCfg()
+        lib().or_comp_get_cfg(self.h, C.byref(g))
+        return {n: getattr(g, n) for n, _ in CompCfg._fields_}
+
     def __del__(self):
         if getattr(self, "h", None):
             lib().or_comp_free(self.h)
@@ -448,9 +469,20 @@ class Expander(Compressor):
             dict(threshold_db=-35.0, ratio=2.0, knee_db=6.0, attack_ms=1.0, release_ms=100.0)
         base.update(kw)
         super().__init__(sample_rate, **base)
-        lib().or_comp_set_expander(self.h, 2 if gate else 1,
-                                   float((-80.0 if gate else -60.0) if range_db is None else range_db),
-                                   float((50.0 if gate else 0.0) if hold_ms is None else hold_ms))
+        self.gate = bool(gate)
+        self.range_db = float((-80.0 if gate else -60.0) if range_db is None else range_db)
+        self.hold_ms = float((50.0 if gate else 0.0) if hold_ms is None else hold_ms)
+        lib().or_comp_set_expander(self.h, 2 if gate else 1, self.range_db, self.hold_ms)
+
+    def reconfigure(self, range_db=None, hold_ms=None, **kw):
+        """Core setters as Compressor.reconfigure, plus SetRange / SetHold
+        (gate.go:196-234): the hold counter keeps counting."""
+        if kw:
+            super().reconfigure(**kw)
+        if range_db is not None or hold_ms is not None:
+            self.range_db = self.range_db if range_db is None else float(range_db)
+            self.hold_ms = self.hold_ms if hold_ms is None else float(hold_ms)
+            lib().or_comp_set_expander(self.h, 2 if self.gate else 1, self.range_db, self.hold_ms)
 
     def hold_counter(self):
         return lib().or_comp_hold_counter(self.h)

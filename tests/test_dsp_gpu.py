@@ -262,6 +262,16 @@ def test_gate_setters(gpu):
     g.ProcessInPlace(b)
     want_a = o.process_in_place(x[:2000])
     assert rms(a[0], want_a) <= RMS_TOL
+    # the block after the setters against the oracle driven the same way: the
+    # hold counter, still full at the change (the 100 ms release has not closed
+    # the gate yet), survives SetHold(0) and holds the gate open to the end
+    assert o.hold_counter() == 2400
+    o.reconfigure(hold_ms=0.0)
+    o.reconfigure(range_db=-30.0)
+    want_b = o.process_in_place(x[2000:])
+    assert rms(b[0], want_b) <= RMS_TOL, rms(b[0], want_b)
+    assert float(np.max(np.abs(b[0] - want_b))) < 1e-12
+    np.testing.assert_allclose(np.array(g.Metrics(0)), np.array(o.metrics()), rtol=METRIC_RTOL, atol=0)
     assert np.all(np.abs(b[0]) <= np.abs(x[2000:]) + 1e-15)
     assert np.min(np.abs(b[0][-500:]) / np.maximum(np.abs(x[2000:][-500:]), 1e-300)) >= 10 ** (-30 / 20) - 1e-12
     with pytest.raises(Exception):

@@ -489,6 +489,163 @@ def test_expander_gain_behaviour():
     assert fb != ff
 
 
+# ------------------------------------------------------------------ dynamics setters mid-stream (or_comp_set_cfg)
+_NONFINITE = {"nan": float("nan"), "inf": float("inf"), "-inf": float("-inf")}
+
+
+def _kat_value(v):
+    return _NONFINITE[v] if isinstance(v, str) else float(v)
+
+
+def test_dynamics_setter_kats():
+    """compressor_test.go:74-290, gate_test.go:199-291: a value a setter accepts
+    is what the getter returns afterwards, and the derived parameters follow
+    it; SetMakeupGain leaves AutoMakeup() false and the makeup at the value
+    (on a default compressor, whose auto makeup is on); SetAutoMakeup toggles.
+    The oracle does not validate: the values the setters reject (and accept)
+    go through the product's host-side ad_compressor_validate here, the
+    gate's hold and range limits through the device setters in
+    test_dynamics_space_gpu.py."""
+    import ctypes as C
+
+    from algodsp import _lib
+
+    def validate(**kv):  # host only: no device needed
+        cfg = _lib.CompressorConfig()
+        _lib.lib().ad_compressor_default_config(C.byref(cfg), float(fs))
+        for n, v in kv.items():
+            setattr(cfg, n, v)
+        return _lib.lib().ad_compressor_validate(C.byref(cfg))
+
+    c = KATS["dynamics_setters"]
+    fs = c["sample_rate"]
+    for field, vals in list(c["compressor"].items()) + [("release_ms", c["gate"]["release_ms"])]:
+        for v in vals["valid"]:
+            assert validate(**{field: _kat_value(v)}) == _lib.AD_OK, (field, v)
+        for v in vals["invalid"]:
+            assert validate(**{field: _kat_value(v)}) == _lib.AD_ERR_INVALID_ARGUMENT, (field, v)
+    for field, vals in c["compressor"].items():
+        comp = O.Compressor(fs)
+        for v in vals["valid"]:
+            if field == "makeup_db":
+                comp.set_makeup_gain(v)
+                assert comp.config()["auto_makeup"] == 0
+                assert comp.params()[4] == 10 ** (v / 20.0)
+            else:
+                comp.reconfigure(**{field: float(v)})
+            assert comp.config()[field] == v
+            fresh = O.Compressor(fs, **{n: x for n, x in comp.config().items() if n != "sample_rate"})
+            assert comp.params() == fresh.params()
+    assert c["makeup_gain_disables_auto_makeup"]
+    comp = O.Compressor(fs)
+    auto_lin = comp.params()[4]
+    for on in c["auto_makeup_toggle"]:
+        comp.reconfigure(auto_makeup=int(on))
+        assert comp.config()["auto_makeup"] == int(on)
+        assert comp.params()[4] == (auto_lin if on else 1.0)
+    for field, vals in c["gate"].items():
+        g = O.Expander(fs, gate=True, threshold_db=-20.0, attack_ms=0.1, knee_db=0.0)
+        for v in vals["valid"]:
+            g.reconfigure(**{field: float(v)})
+            if field == "range_db":
+                assert g.gain(0.0) == 10 ** (v / 20.0)
+            elif field == "hold_ms":
+                for _ in range(200):
+                    g.process_sample(0.5)
+                assert g.hold_counter() == int(v * 0.001 * fs)
+            else:
+                assert g.config()[field] == v
+
+
+CFG_MIDSTREAM = [
+    ("compressor", {}),
+    ("compressor", {"detector_mode": 1, "rms_window_ms": 5.0, "sidechain_low_cut_hz": 80.0,
+                    "sidechain_high_cut_hz": 6000.0}),
+    ("compressor", {"topology": 1}),
+    ("gate", {"threshold_db": -20.0, "attack_ms": 0.1, "release_ms": 1.0, "hold_ms": 20.0, "knee_db": 0.0}),
+    ("expander", {"detector_mode": 1, "rms_window_ms": 20.0}),
+]
+
+
+def _dyn(kind, cfg, fs=48000.0):
+    return O.Compressor(fs, **cfg) if kind == "compressor" else O.Expander(fs, gate=kind == "gate", **cfg)
+
+
+def _burst(n, seed, hi=0.5, lo=0.003, period=900):
+    return np.where((np.arange(n) // period) % 2 == 0, hi, lo) * signals.white_noise(n, seed)
+
+
+@pytest.mark.parametrize("kind,cfg", CFG_MIDSTREAM, ids=[f"{k}-{i}" for i, (k, _) in enumerate(CFG_MIDSTREAM)])
+def test_set_cfg_unchanged_config_is_transparent(kind, cfg):
+    """or_comp_set_cfg / or_comp_set_expander with the config the core already
+    has, in the middle of a stream (for the gate: while the hold counts down),
+    leave the following output and the metrics bit-identical."""
+    x = _burst(4000, 3)
+    cut = 1300  # 400 samples into a quiet stretch: the gate's 960-sample hold is counting
+    one = _dyn(kind, cfg)
+    want = one.process_in_place(x)
+    two = _dyn(kind, cfg)
+    a = two.process_in_place(x[:cut])
+    if kind == "gate":
+        assert 0 < two.hold_counter() < 960
+    two.reconfigure(**{n: v for n, v in two.config().items() if n != "sample_rate"})
+    if kind != "compressor":
+        two.reconfigure(range_db=two.range_db, hold_ms=two.hold_ms)
+    b = two.process_in_place(x[cut:])
+    assert np.array_equal(np.concatenate([a, b]).view(np.uint64), want.view(np.uint64))
+    assert one.metrics() == two.metrics()
+
+
+def test_set_cfg_state_semantics():
+    """What the reference's setters keep and clear (core.go:186-250, 500-518,
+    606-650; gate.go:196-234): SetRMSWindow in peak mode changes nothing
+    audible; in RMS mode it restarts the ring alone (the envelope carries on,
+    so the output right after differs from a reset core's); a cut set to 0 and
+    back starts that filter from zero, a cut moved between positive values
+    keeps its state; SetHold / SetRange keep the hold counter."""
+    x = _burst(3000, 4)
+    want = O.Compressor(48000.0).process_in_place(x)
+    c = O.Compressor(48000.0)
+    a = c.process_in_place(x[:1200])
+    c.reconfigure(rms_window_ms=5.0)
+    assert np.array_equal(np.concatenate([a, c.process_in_place(x[1200:])]), want)
+
+    # RMS mode: the new ring is empty (level restarts low), the envelope is not reset
+    c = O.Compressor(48000.0, detector_mode=1, rms_window_ms=30.0, auto_makeup=0)
+    c.process_in_place(np.full(3000, 0.5))
+    c.reconfigure(rms_window_ms=5.0)
+    y = c.process_sample(0.5)
+    r = O.Compressor(48000.0, detector_mode=1, rms_window_ms=5.0, auto_makeup=0)
+    assert y < r.process_sample(0.5) <= 0.5  # envelope kept: still compressing
+    # one sample into a 240-slot ring: mean = 0.25 / 240, below the 0.5 envelope -> release branch
+    assert c.metrics()[2] < 1.0
+
+    # side-chain cut: 0 clears the one-pole, another positive value keeps it
+    def run(mid):
+        c = O.Compressor(48000.0, sidechain_high_cut_hz=2000.0, attack_ms=0.1)
+        c.process_in_place(x[:1200])
+        c.reconfigure(sidechain_high_cut_hz=mid)
+        c.reconfigure(sidechain_high_cut_hz=2000.0)
+        return c.process_in_place(x[1200:1300])
+    kept, cleared = run(3000.0), run(0.0)
+    base = O.Compressor(48000.0, sidechain_high_cut_hz=2000.0, attack_ms=0.1).process_in_place(x[:1300])[1200:]
+    assert np.array_equal(kept, base)
+    assert not np.array_equal(cleared, base)
+
+    # gate: SetHold / SetRange while the hold counts down
+    g = O.Expander(48000.0, gate=True, threshold_db=-20.0, attack_ms=0.1, release_ms=1.0, hold_ms=10.0, knee_db=0.0)
+    g.process_in_place(np.full(2000, 0.5))
+    g.process_in_place(np.zeros(300))
+    left = g.hold_counter()
+    assert 0 < left < 480
+    g.reconfigure(hold_ms=0.0)
+    g.reconfigure(range_db=-30.0)
+    assert g.hold_counter() == left
+    y = g.process_in_place(np.full(left + 5, 1e-4))  # below threshold: held open until the counter runs out
+    assert np.all(y[:left] == 1e-4) and np.all(y[left:] < 1e-4)
+    assert g.hold_counter() == 0
+
+
 # ---------------------------------------------------------- float32 variants
 def test_oracle_streaming32_kats():
     """The float32 restatement (or_conv32.c) against the reference's own float32
