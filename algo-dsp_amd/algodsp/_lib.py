@@ -243,6 +243,16 @@ def _declare(L: C.CDLL) -> None:
         "ad_fir_process_device": (C.c_int, [vp, vp, i64, vp, i64, i64, vp]),
         "ad_fir_reset": (C.c_int, [vp]),
         "ad_fir_destroy": (None, [vp]),
+        "ad_resampler_create": (C.c_int, [i64, i64, c_double_p, i64, C.c_int, C.c_int, C.POINTER(vp)]),
+        "ad_resampler_predict_output_len": (C.c_int, [vp, i64, c_int64_p]),
+        "ad_resampler_process": (C.c_int, [vp, c_double_p, i64, c_double_p, i64, c_int64_p]),
+        "ad_resampler_process_device": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, c_int64_p, vp]),
+        "ad_resampler_reset": (C.c_int, [vp]),
+        "ad_resampler_ratio": (C.c_int, [vp, c_int64_p, c_int64_p]),
+        "ad_resampler_taps_per_phase": (C.c_int, [vp]),
+        "ad_resampler_kernel_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int), C.POINTER(C.c_int), c_int64_p]),
+        "ad_resampler_destroy": (None, [vp]),
         "ad_correlate_fft": (C.c_int, [c_double_p, i64, c_double_p, i64, c_double_p, C.c_int]),
         "ad_correlate_fft_device": (C.c_int, [vp, i64, vp, i64, vp, C.c_int, vp]),
         "ad_deconv_default_options": (DeconvOptionsC, []),

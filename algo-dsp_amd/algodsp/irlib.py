@@ -152,10 +152,18 @@ def large_church(path=DEFAULT_IRLIB, pad_to: int | None = 131072) -> np.ndarray:
 class LibraryProvider:
     """effectchain.IRProvider over an IR library (internal/webdemo
     effects_chain_adapter.go:12-23 + irlib.go:59-65): GetIR(index) returns
-    (samples [ch][n], sample_rate, ok); ok is False out of range."""
+    (samples [ch][n], sample_rate, ok); ok is False out of range.
 
-    def __init__(self, path=DEFAULT_IRLIB, gpu: bool = False):
+    With `target_rate`, an IR stored at another rate is returned resampled to
+    it on the GPU (resample.NewForRates at Balanced quality, all of the IR's
+    channels in one call) together with the target rate, so a session at
+    44.1 or 96 kHz convolves with an IR of the right pitch and length."""
+
+    def __init__(self, path=DEFAULT_IRLIB, gpu: bool = False, target_rate: float | None = None, device: int = 0):
         self.irs = read_irlib(path, gpu=gpu)
+        self.target_rate = target_rate
+        self.device = device
+        self._resampled = {}
 
     def GetIR(self, index: int):
         if index < 0 or index >= len(self.irs):
@@ -163,7 +171,19 @@ class LibraryProvider:
         ir = self.irs[index]
         if ir["samples"] is None or len(ir["samples"]) == 0:
             return None, 0.0, False
-        return ir["samples"], ir["sample_rate"], True
+        if self.target_rate is None or ir["sample_rate"] == self.target_rate:
+            return ir["samples"], ir["sample_rate"], True
+        if index not in self._resampled:
+            from . import resample
+
+            s = ir["samples"]
+            r = resample.NewForRates(ir["sample_rate"], self.target_rate, quality=resample.QualityBalanced,
+                                     channels=s.shape[0], device=self.device)
+            try:
+                self._resampled[index] = r.Process(s)
+            finally:
+                r.close()
+        return self._resampled[index], float(self.target_rate), True
 
     def IRNames(self):
         return [ir["name"] for ir in self.irs]

@@ -596,6 +596,56 @@ int ad_fir_process_device(ad_fir* f, const double* d_src, int64_t src_stride, do
 int ad_fir_reset(ad_fir* f); /* :162-172 */
 void ad_fir_destroy(ad_fir* f);
 
+/* ---- resample.Resampler (dsp/resample/resample.go:134-340) ----------------
+ * Rational polyphase FIR sample-rate conversion, ratio up/down, for `channels`
+ * independent streams that share the prototype and one scalar state (phase,
+ * inputIndex, totalIn: every stream is fed the same block lengths).
+ * create: NewRational (:153-187) with the prototype `taps` designed on the
+ *   host (designPolyphaseFIR, resample_design.go:9-69); the ratio is reduced
+ *   by its gcd, phase p is taps[p], taps[p+up], ..., so n_taps must be a
+ *   positive multiple of the reduced up (T = n_taps/up taps per phase, a
+ *   delay line of T-1 samples per channel).  up, down or channels <= 0, a
+ *   reduced up or down above 2^30, such an n_taps, or a non-finite tap ->
+ *   AD_ERR_INVALID_ARGUMENT, all before any device is touched.
+ * predict_output_len: PredictOutputLen (:295-313) for the next call, in closed
+ *   form: 0 for n_in <= 0 or L = totalIn + n_in - inputIndex <= 0, else
+ *   ceil((L*up - phase) / down).
+ * process: Process (:249-292).  Output j of a call is
+ *   y = sum_k phases[(phase + j*down) % up][k] * x[inputIndex + (phase + j*down)/up - k],
+ *   k ascending from y = 0, a rounded product and a rounded add per term (no
+ *   FMA), bit for bit the reference's loop; samples before the stream start
+ *   count as +0.  Host form: in [channels][n_in], out [channels][*n_out]
+ *   packed at row length *n_out.  Device form: rows of n_in at in_stride and
+ *   of *n_out at out_stride under the "Device buffers" contract above; only
+ *   *n_out elements of each output row are written; input and output must not
+ *   overlap (AD_ERR_INVALID_ARGUMENT).  out_cap is the room per output row:
+ *   out_cap < the predicted length -> AD_ERR_INVALID_ARGUMENT with the state
+ *   and the outputs untouched.  n_in == 0 does nothing; a call that yields
+ *   *n_out == 0 (down > up and fewer samples than the next input index needs)
+ *   writes nothing and still takes the samples in.  n_in must be < 2^31 and a
+ *   call may produce at most 2^38 outputs; with the bounds on up and down
+ *   every index product stays inside int64.
+ * Calls on different streams are serialised through an event, as ad_fir's.
+ * reset: Reset (:241-246), ordered after the last call.
+ * kernel_info: the launch layout fixed at create -- outputs per tile, tiles a
+ *   workgroup walks, whether the coefficient table and the input window are
+ *   staged in LDS (else read from global memory), whether the next window is
+ *   loaded while a tile computes, and the LDS bytes per workgroup.           */
+typedef struct ad_resampler ad_resampler;
+int ad_resampler_create(int64_t up, int64_t down, const double* taps, int64_t n_taps, int channels, int device,
+                        ad_resampler** out);
+int ad_resampler_predict_output_len(const ad_resampler* r, int64_t n_in, int64_t* n_out);
+int ad_resampler_process(ad_resampler* r, const double* in, int64_t n_in, double* out, int64_t out_cap,
+                         int64_t* n_out);
+int ad_resampler_process_device(ad_resampler* r, const double* d_in, int64_t in_stride, int64_t n_in, double* d_out,
+                                int64_t out_stride, int64_t out_cap, int64_t* n_out, void* stream);
+int ad_resampler_reset(ad_resampler* r);
+int ad_resampler_ratio(const ad_resampler* r, int64_t* up, int64_t* down); /* :316-318 */
+int ad_resampler_taps_per_phase(const ad_resampler* r);                    /* :326-332 */
+int ad_resampler_kernel_info(const ad_resampler* r, int* tile, int* tiles_per_workgroup, int* table_in_lds,
+                             int* window_in_lds, int* window_prefetch, int64_t* lds_bytes);
+void ad_resampler_destroy(ad_resampler* r);
+
 /* ---- spectral correlation / deconvolution (dsp/conv/correlate.go,
  * dsp/conv/deconvolve.go) --------------------------------------
  * One power-of-two FFT over the whole zero-padded signal, as the reference's
