@@ -113,9 +113,34 @@ struct SpectralRun {
   // inverse of the Hermitian product at half length (N >= 32: both plans
   // have passes)
   bool fused() const { return N >= 32; }
+  // One transform of a + i b is not exactly Hermitian-separable in floating
+  // point: the rounded twiddles of output q and of its mirror N - q are not
+  // each other's conjugates, so a fraction rho ~ eps of each signal leaks into
+  // the other, coherently (the same twiddle multiplies every sample that
+  // meets it).  After the max-abs normalisation the leak of a adds
+  // rho |a'|_2^2 to a lag, against lags of size ~ |a'|_2 |b'|_2 / sqrt(N):
+  // harmless for signals of comparable energy (rho sqrt(N) relative), but a
+  // dense signal against one tap, or against an impulse in a long array,
+  // loses rho |a'|_2^2 / |b'|_2, measured 1.6e-10 of the largest lag at
+  // N = 2^25 and 1e-9 at 2^27 (tests/test_spectral_plans_gpu.py).  So the
+  // packed transform is taken only below 2^25 and while max(n, m) <=
+  // 2^17 sqrt(min(n, m)), which keeps that loss under a tenth of the 1e-10
+  // parity bar for dense signals; otherwise a and b are transformed
+  // separately, as Deconvolve's are (error ~ 3 err_scale at every size).
+  bool packs(int64_t n, int64_t m) const {
+    const int64_t mx = n > m ? n : m, mn = n > m ? m : n;
+    return N < ((int64_t)1 << 25) && mx * mx <= ((int64_t)1 << 34) * mn;
+  }
   void correlate(const double* a, int64_t n, const double* b, int64_t m, double* out, hipStream_t s) {
     auto& h = dc.plans[N / 2];
     if (!h) h.reset(new BigFft(N / 2));
+    if (!packs(n, m)) {
+      dc.spec.reserve((size_t)(2 * N));
+      dc.scratch.reserve((size_t)(4 * N));
+      fft->spectral_half(*h, kSpecCorr, 0.0, nullptr, false, a, n, b, m, n, m - 1, N - m + 1, dc.spec.p, out,
+                         dc.scratch.p, s);
+      return;
+    }
     dc.spec.reserve((size_t)N);
     dc.scratch.reserve((size_t)(2 * N));
     if (dc.amax.n < (size_t)kAbsmaxWords) {  // zeroed once: the kernel resets its counter itself

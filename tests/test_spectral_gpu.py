@@ -131,7 +131,9 @@ def test_correlate_fft_2p24(gpu, n, m, sa, sb):
     equal, 1e7-apart and 2^1200-apart scales.  Checked against numpy's fp64
     FFT at the spectral bar: the oracle's C restatement takes ~30 s per call
     at this size, and test_oracle.py::test_correlate_fft_matches_numpy pins it
-    to the same numpy expression at smaller sizes."""
+    to the same numpy expression at smaller sizes.  (The third case's 10-sample
+    b is past SpectralRun::packs' length ratio and takes two transforms; the
+    split pass at 2^+-600 scales is run by test_spectral_plans_gpu.py.)"""
     a, b = sa * signals.white_noise(n, 5 + n), sb * signals.white_noise(m, 6 + m)
     close(conv.CorrelateFFT(a, b), _np_correlate_fft(a, b))
 
