@@ -103,6 +103,13 @@ class CompressorConfig(C.Structure):
                [(n, C.c_int) for n in ("topology", "detector_mode", "feedback_ratio_scale", "auto_makeup")]
 
 
+class FdnConfig(C.Structure):
+    """ad_fdn_config (include/algodsp.h); field k is parameter AD_FDN_* = k."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "wet", "dry", "rt60_seconds", "damp", "pre_delay_seconds",
+                                          "mod_depth_seconds", "mod_rate_hz")]
+
+
 class DeconvOptionsC(C.Structure):
     """ad_deconv_options (include/algodsp.h)."""
 
@@ -253,6 +260,17 @@ def _declare(L: C.CDLL) -> None:
         "ad_resampler_kernel_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                C.POINTER(C.c_int), C.POINTER(C.c_int), c_int64_p]),
         "ad_resampler_destroy": (None, [vp]),
+        "ad_fdn_default_config": (None, [C.POINTER(FdnConfig), C.c_double]),
+        "ad_fdn_validate": (C.c_int, [C.POINTER(FdnConfig)]),
+        "ad_fdn_create": (C.c_int, [C.POINTER(FdnConfig), C.c_int, C.c_int, C.POINTER(vp)]),
+        "ad_fdn_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
+        "ad_fdn_get_config": (C.c_int, [vp, C.POINTER(FdnConfig)]),
+        "ad_fdn_derived": (C.c_int, [vp, c_double_p, c_int64_p, c_int64_p, c_double_p]),
+        "ad_fdn_kernel_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "ad_fdn_process": (C.c_int, [vp, c_double_p, i64]),
+        "ad_fdn_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
+        "ad_fdn_reset": (C.c_int, [vp]),
+        "ad_fdn_destroy": (None, [vp]),
         "ad_correlate_fft": (C.c_int, [c_double_p, i64, c_double_p, i64, c_double_p, C.c_int]),
         "ad_correlate_fft_device": (C.c_int, [vp, i64, vp, i64, vp, C.c_int, vp]),
         "ad_deconv_default_options": (DeconvOptionsC, []),

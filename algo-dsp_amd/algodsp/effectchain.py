@@ -13,8 +13,8 @@ its runtime's Configure does (runtime_dynamics.go, runtime_filter_pitch_reverb.g
 chain_process.go:177-227 for split-freq).  The compiled node list goes to
 ad_fx_graph_create (include/algodsp.h), which runs every node on the GPU;
 there is no CPU path.  Node types outside {filter*, dyn-compressor,
-dyn-limiter, dyn-gate, dyn-expander, reverb-freeverb, split-freq, split, sum,
-_input, _output} raise
+dyn-limiter, dyn-gate, dyn-expander, reverb-freeverb, reverb-fdn, reverb,
+reverb-conv, split-freq, split, sum, _input, _output} raise
 UnknownEffect (the GPU runtime's ErrUnknownEffect).
 """
 from __future__ import annotations
@@ -26,7 +26,7 @@ import math
 import numpy as np
 
 from . import design
-from ._lib import CompressorConfig, check, lib, ptr
+from ._lib import CompressorConfig, FdnConfig, check, lib, ptr
 from .processors import section_table
 
 INPUT_NODE_ID = "_input"  # graph.go:10-13
@@ -34,6 +34,7 @@ OUTPUT_NODE_ID = "_output"
 NODE_TYPE_SPLIT_FREQ = "split-freq"
 
 FXN_INPUT, FXN_OUTPUT, FXN_PASS, FXN_SPLIT_FREQ, FXN_BIQUAD, FXN_COMPRESSOR, FXN_FREEVERB, FXN_CONV_REVERB = range(8)
+FXN_FDN_REVERB = 8
 MAX_PARENTS = 8
 
 FILTER_TYPES = ("filter", "filter-lowpass", "filter-highpass", "filter-bandpass", "filter-notch",
@@ -56,7 +57,7 @@ class _Node(C.Structure):
                 ("comp", C.POINTER(CompressorConfig)), ("verb", C.c_double * 5),
                 ("dyn_mode", C.c_int), ("dyn_range_db", C.c_double), ("dyn_hold_ms", C.c_double),
                 ("ir", C.POINTER(C.c_double)), ("ir_len", C.c_int64), ("conv_min_order", C.c_int),
-                ("conv_wet", C.c_double), ("conv_dry", C.c_double)]
+                ("conv_wet", C.c_double), ("conv_dry", C.c_double), ("fdn", C.POINTER(FdnConfig))]
 
 
 def clamp(v, lo, hi):  # core.Clamp
@@ -202,6 +203,22 @@ def freeverb_params(p: Params):
     return (clamp(p.GetNum("wet", 0.22), 0, 1.5), clamp(p.GetNum("dry", 1), 0, 1.5),
             clamp(p.GetNum("roomSize", 0.72), 0, 0.98), clamp(p.GetNum("damp", 0.45), 0, 0.99),
             clamp(p.GetNum("gain", 0.015), 0, 0.1))
+
+
+def fdn_params(p: Params, fs: float) -> FdnConfig:
+    """fdnReverbRuntime.Configure (runtime_filter_pitch_reverb.go:351-363): the
+    clamped values configureFDNReverb hands to the setters of a
+    NewFDNReverb(fs).  Its wet and damp defaults are not NewFDNReverb's."""
+    c = FdnConfig()
+    c.sample_rate = float(fs)
+    c.wet = clamp(p.GetNum("wet", 0.22), 0, 1.5)
+    c.dry = clamp(p.GetNum("dry", 1), 0, 1.5)
+    c.rt60_seconds = clamp(p.GetNum("rt60", 1.8), 0.2, 8)
+    c.pre_delay_seconds = clamp(p.GetNum("preDelay", 0.01), 0, 0.1)
+    c.damp = clamp(p.GetNum("damp", 0.45), 0, 0.99)
+    c.mod_depth_seconds = clamp(p.GetNum("modDepth", 0.002), 0, 0.01)
+    c.mod_rate_hz = clamp(p.GetNum("modRate", 0.1), 0, 1)
+    return c
 
 
 def _filter_kind(node_type, raw):  # normalizeFilterKind normalize.go:42-86
@@ -376,7 +393,13 @@ class Chain:
                 d.dyn_mode, d.dyn_range_db, d.dyn_hold_ms = (2 if gate else 1), rng, hold
                 sd.update(type="comp", comp={f: getattr(cfg, f) for f, _ in cfg._fields_},
                           expander=dict(gate=gate, range_db=rng, hold_ms=hold))
-            elif t == "reverb-freeverb":
+            elif t == "reverb-fdn" or (t == "reverb" and p.Str.get("model") == "fdn"):
+                d.type = FXN_FDN_REVERB
+                cfg = fdn_params(p, fs)
+                keep.append(cfg)
+                d.fdn = C.pointer(cfg)
+                sd.update(type="fdn", fdn={f: getattr(cfg, f) for f, _ in cfg._fields_})
+            elif t in ("reverb-freeverb", "reverb"):  # reverbRuntime without model "fdn" is Freeverb
                 d.type = FXN_FREEVERB
                 for j, v in enumerate(freeverb_params(p)):
                     d.verb[j] = v

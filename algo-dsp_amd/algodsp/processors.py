@@ -6,6 +6,7 @@ like the reference's own tests:
   biquad.Chain / biquad.Section  dsp/filter/biquad/chain.go, section.go
   dynamics.Compressor            dsp/effects/dynamics/compressor.go
   reverb.Reverb (Freeverb)       dsp/effects/reverb/reverb.go
+  reverb.FDNReverb               dsp/effects/reverb/fdn_reverb.go
   fir.Filter                     dsp/filter/fir/filter.go
   effectchain filter -> dyn-compressor -> reverb-freeverb (EffectChain)
 
@@ -19,7 +20,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CompressorConfig, check, f64, lib, ptr
+from ._lib import CompressorConfig, FdnConfig, check, f64, lib, ptr
 
 DEVICE = 0
 SEC_STRIDE = 6  # {pre_gain, b0, b1, b2, a1, a2}
@@ -291,6 +292,120 @@ class Reverb(_FxChain):
 
     def ProcessInPlace(self, buf):  # reverb.go:185-189
         self._process(buf)
+
+
+class FDNReverb:
+    """reverb.FDNReverb (fdn_reverb.go:37-391) for `channels` instances sharing
+    one configuration: NewFDNReverb(sample_rate), or `config` (an FdnConfig)
+    applied whole.  The setters are the reference's, side effects included
+    (ad_fdn_set_param); a rejected value raises ErrInvalidArgument and changes
+    nothing."""
+
+    P_SAMPLE_RATE, P_WET, P_DRY, P_RT60, P_DAMP, P_PRE_DELAY, P_MOD_DEPTH, P_MOD_RATE = range(8)  # AD_FDN_*
+
+    def __init__(self, sample_rate: float = 44100.0, channels: int = 1, device: int = DEVICE, config=None):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        cfg = FdnConfig()
+        if config is None:
+            lib().ad_fdn_default_config(C.byref(cfg), float(sample_rate))
+        else:
+            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        check(lib().ad_fdn_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+
+    def _set(self, which: int, v):
+        check(lib().ad_fdn_set_param(self._h, which, float(v)))
+
+    def config(self) -> FdnConfig:
+        cfg = FdnConfig()
+        check(lib().ad_fdn_get_config(self._h, C.byref(cfg)))
+        return cfg
+
+    def SetSampleRate(self, v):  # :95-106
+        self._set(self.P_SAMPLE_RATE, v)
+
+    def SetWet(self, v):  # :109-117
+        self._set(self.P_WET, v)
+
+    def SetDry(self, v):  # :120-128
+        self._set(self.P_DRY, v)
+
+    def SetRT60(self, v):  # :131-140
+        self._set(self.P_RT60, v)
+
+    def SetDamp(self, v):  # :143-151
+        self._set(self.P_DAMP, v)
+
+    def SetPreDelay(self, v):  # :154-163
+        self._set(self.P_PRE_DELAY, v)
+
+    def SetModDepth(self, v):  # :166-175
+        self._set(self.P_MOD_DEPTH, v)
+
+    def SetModRate(self, v):  # :178-186
+        self._set(self.P_MOD_RATE, v)
+
+    def SampleRate(self) -> float:  # :251-272
+        return self.config().sample_rate
+
+    def Wet(self) -> float:
+        return self.config().wet
+
+    def Dry(self) -> float:
+        return self.config().dry
+
+    def RT60(self) -> float:
+        return self.config().rt60_seconds
+
+    def Damp(self) -> float:
+        return self.config().damp
+
+    def PreDelay(self) -> float:
+        return self.config().pre_delay_seconds
+
+    def ModDepth(self) -> float:
+        return self.config().mod_depth_seconds
+
+    def ModRate(self) -> float:
+        return self.config().mod_rate_hz
+
+    def derived(self):
+        """(feedback gains [8], line lengths [8], pre-delay line length, LFO
+        phase): what reconfigureDelays / updateFeedbackGains derived, and the
+        phase after the last call (ad_fdn_derived)."""
+        g = np.zeros(8)
+        ln = np.zeros(8, dtype=np.int64)
+        pl, ph = C.c_int64(), C.c_double()
+        check(lib().ad_fdn_derived(self._h, ptr(g), ln.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(pl),
+                                   C.byref(ph)))
+        return g, ln, pl.value, ph.value
+
+    def kernel_info(self):
+        """(block, sub_block, lds_bytes) of ad_fdn_kernel_info."""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        check(lib().ad_fdn_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def ProcessInPlace(self, buf):  # :244-248
+        b = _as2d(buf, self.channels)
+        check(lib().ad_fdn_process(self._h, ptr(b), b.shape[1]))
+
+    def process_device(self, d_buf: int, stride: int, n: int, stream: int | None = None):
+        check(lib().ad_fdn_process_device(self._h, C.c_void_p(d_buf), int(stride), int(n), C.c_void_p(stream or 0)))
+
+    def Reset(self):  # :189-197
+        check(lib().ad_fdn_reset(self._h))
+
+    def close(self):
+        if self._h:
+            lib().ad_fdn_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class EffectChain(_FxChain):

@@ -56,12 +56,18 @@ struct ConvDel {
 };
 using ConvPtr = std::unique_ptr<ad_conv, ConvDel>;
 
+struct FdnDel {
+  void operator()(ad_fdn* f) const { ad_fdn_destroy(f); }
+};
+using FdnPtr = std::unique_ptr<ad_fdn, FdnDel>;
+
 struct FxOp {
-  enum Kind { ZERO, COPY, MIX, CHAIN, CONV } kind;
-  int dst = -1;                 // buffer id (written; CHAIN / CONV: read and written in place)
+  enum Kind { ZERO, COPY, MIX, CHAIN, CONV, FDN } kind;
+  int dst = -1;                 // buffer id (written; CHAIN / CONV / FDN: read and written in place)
   std::vector<int> srcs;        // COPY / MIX: buffers read
   ad_fx_chain* chain = nullptr;   // CHAIN
   ad_conv* conv = nullptr;        // CONV (many-channel convolution reverb)
+  ad_fdn* fdn = nullptr;          // FDN (many-channel FDN reverb)
   // schedule (see schedule()): lane 0 is the caller's stream
   int lane = 0;
   std::vector<int> waits;  // ops on other lanes this op waits for
@@ -88,6 +94,7 @@ struct ad_fx_graph {
   std::vector<FxOp> ops;
   std::vector<ChainPtr> chains;
   std::vector<ConvPtr> convs;
+  std::vector<FdnPtr> fdns;
   DevBuf<double> pool;   // buffers 1..nbuf-1, [nbuf-1][channels][cap]
   int64_t cap = 0;
   DevBuf<double> work;   // host-call staging
@@ -107,6 +114,7 @@ struct ad_fx_graph {
       }
     chains.clear();
     convs.clear();
+    fdns.clear();
     if (stream) {
       (void)hipStreamSynchronize(stream);
       (void)lib_stream_destroy(stream);
@@ -151,7 +159,7 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, int n) {
   int out_node = -1;
   for (int i = 0; i < n; ++i) {
     const ad_fx_node& d = nodes[i];
-    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_CONV_REVERB)
+    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_FDN_REVERB)
       AD_FAIL(AD_ERR_UNKNOWN_EFFECT, "fx graph: node type not supported by the GPU runtime");
     if (d.type == AD_FXN_INPUT && i != 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: more than one input node");
     if (d.type == AD_FXN_OUTPUT) {
@@ -175,6 +183,7 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, int n) {
     if (d.type == AD_FXN_COMPRESSOR && !d.comp) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: compressor without config");
     if (d.type == AD_FXN_CONV_REVERB && !d.bypassed && (!d.ir || d.ir_len <= 0))
       AD_FAIL(AD_ERR_EMPTY_IMPULSE_RESPONSE, "fx graph: reverb-conv node without an impulse response");
+    if (d.type == AD_FXN_FDN_REVERB && !d.fdn) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: reverb-fdn node without config");
     if (d.type == AD_FXN_COMPRESSOR && (d.dyn_mode < 0 || d.dyn_mode > 2))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: bad dynamics mode");
   }
@@ -237,6 +246,17 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, int n) {
       g->ops.push_back(op);
       continue;
     }
+    if (d.type == AD_FXN_FDN_REVERB) {
+      flush(g, gr);
+      ad_fdn* fr = nullptr;
+      ck(ad_fdn_create(d.fdn, g->channels, g->device, &fr));
+      g->fdns.emplace_back(fr);
+      FxOp op{FxOp::FDN};
+      op.dst = b;
+      op.fdn = fr;
+      g->ops.push_back(op);
+      continue;
+    }
     const int lvl = d.type == AD_FXN_BIQUAD ? 1 : (d.type == AD_FXN_COMPRESSOR ? 2 : 3);
     if (gr.open && (lvl < gr.level() || (lvl == gr.level() && lvl > 1))) flush(g, gr);
     gr.open = true;
@@ -276,7 +296,7 @@ void schedule(ad_fx_graph* g) {
   for (int i = 0; i < (int)g->ops.size(); ++i) {
     FxOp& op = g->ops[i];
     std::vector<int> reads = op.srcs;
-    if (op.kind == FxOp::CHAIN || op.kind == FxOp::CONV) reads.push_back(op.dst);
+    if (op.kind == FxOp::CHAIN || op.kind == FxOp::CONV || op.kind == FxOp::FDN) reads.push_back(op.dst);
     std::vector<int> deps;
     for (int b : reads)
       if (last_writer[b] >= 0) deps.push_back(last_writer[b]);
@@ -370,6 +390,9 @@ void run(ad_fx_graph* g, double* d0, int64_t stride0, int64_t n, hipStream_t s) 
       case FxOp::CONV:
         ck(ad_conv_reverb_multi_process_device(op.conv, dst, st(op.dst), n, ls));
         break;
+      case FxOp::FDN:
+        ck(ad_fdn_process_device(op.fdn, dst, st(op.dst), n, ls));
+        break;
     }
     if (op.signal) AD_HIP(hipEventRecord(g->op_ev[i], ls));
   }
@@ -446,6 +469,7 @@ int ad_fx_graph_reset(ad_fx_graph* g) {
   return graph_guard(g, [&] {
     for (auto& c : g->chains) ck(ad_fx_chain_reset(c.get()));
     for (auto& c : g->convs) ck(ad_conv_reset(c.get()));
+    for (auto& f : g->fdns) ck(ad_fdn_reset(f.get()));
   });
 }
 

@@ -523,7 +523,9 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
  *   AD_FXN_FREEVERB    reverb.Reverb.ProcessInPlace, verb = {wet, dry,
  *                      room_size, damp, gain} (runtime_filter_pitch_reverb.go:330-345);
  *   AD_FXN_CONV_REVERB reverb.ConvolutionReverb.ProcessInPlace (reverb-conv,
- *                      runtime_misc.go:61-67) on the many-channel partitioned engine.
+ *                      runtime_misc.go:61-67) on the many-channel partitioned engine;
+ *   AD_FXN_FDN_REVERB  reverb.FDNReverb.ProcessInPlace (reverb-fdn,
+ *                      runtime_filter_pitch_reverb.go:366-368) on the FDN kernel.
  * The result is the output node's buffer.  Linear runs of in-place nodes fuse
  * into one launch (bit-identical, see capi_fxgraph.cpp).  Other node types
  * return AD_ERR_UNKNOWN_EFFECT; the configs are copied at create.          */
@@ -537,7 +539,11 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
 #define AD_FXN_CONV_REVERB 7 /* reverb-conv (runtime_misc.go:12-67): ConvolutionReverb(ir, conv_min_order)
                                 with SetWetDry(conv_wet, conv_dry), in place; the caller
                                 mono-averages the provider's IR as Configure does */
+#define AD_FXN_FDN_REVERB 8 /* reverb-fdn, and reverb with model "fdn" (runtime_filter_pitch_reverb.go:347-395):
+                               FDNReverb.ProcessInPlace configured by *fdn (ad_fdn_config, below), an op
+                               of its own on the many-channel FDN kernel */
 #define AD_FX_MAX_PARENTS 8
+struct ad_fdn_config;
 typedef struct ad_fx_node {
   int type;
   int bypassed;
@@ -557,6 +563,7 @@ typedef struct ad_fx_node {
   int64_t ir_len;
   int conv_min_order;               /* CONV_REVERB: minBlockOrder (reverb-conv uses 7; maxBlockOrder 13) */
   double conv_wet, conv_dry;        /* CONV_REVERB: SetWetDry(wet, dry) (reverb-conv: wet param, dry 1.0) */
+  const struct ad_fdn_config* fdn;  /* FDN_REVERB */
 } ad_fx_node;
 typedef struct ad_fx_graph ad_fx_graph;
 int ad_fx_graph_create(const ad_fx_node* nodes, int n_nodes, int channels, int device, ad_fx_graph** out);
@@ -645,6 +652,65 @@ int ad_resampler_taps_per_phase(const ad_resampler* r);                    /* :3
 int ad_resampler_kernel_info(const ad_resampler* r, int* tile, int* tiles_per_workgroup, int* table_in_lds,
                              int* window_in_lds, int* window_prefetch, int64_t* lds_bytes);
 void ad_resampler_destroy(ad_resampler* r);
+
+/* ---- reverb.FDNReverb (dsp/effects/reverb/fdn_reverb.go:37-391) -------------
+ * The modulated eight-line feedback delay network, for `channels` independent
+ * instances that share one configuration (their samples and state differ).
+ * ProcessSample (:199-241) bit for bit in its operation order -- every
+ * product and sum rounded on its own, no FMA, the LFO phase the reference's
+ * sequence of rounded additions and wraps -- except for the sine of the
+ * modulation, which is the device math library's (within 1e-12 relative RMS
+ * of the reference; with mod depth 0 the outputs are bit-identical).
+ * default_config: NewFDNReverb's defaults (:12-19) at sample_rate.
+ * validate: every setter's range (:95-186), host only: sample rate and RT60
+ *   > 0, damp in [0, 1], the others >= 0, all finite; also refused: a
+ *   configuration whose longest line would exceed 2^27 samples.
+ * create: validation first (AD_ERR_INVALID_ARGUMENT), then the device
+ *   (AD_ERR_NO_DEVICE without one).
+ * set_param: the named setter with its side effects.  SAMPLE_RATE, PRE_DELAY
+ *   and MOD_DEPTH run reconfigureDelays (:274-301): every damping state is
+ *   zeroed, a line whose length changes (max(ceil(base_i*scale + depth) + 3, 4))
+ *   is replaced by a zeroed one, the others keep their contents, the feedback
+ *   gains are recomputed, the LFO phase stays.  RT60 recomputes the gains; WET,
+ *   DRY, DAMP and MOD_RATE only store (they take effect with the next call).
+ *   A rejected value changes nothing.  A reconfiguring setter waits for the
+ *   handle's last call.
+ * derived: the feedback gains pow(10, -3*delaySeconds/rt60) (:303-312), the
+ *   lines' and the pre-delay line's buffer lengths, and the LFO phase after the
+ *   last call (waits for it).  Any pointer may be NULL.
+ * kernel_info: `block` = max(1, floor(1537 * sample_rate / 44100)) consecutive
+ *   samples of a channel read none of each other's writes; the kernel walks a
+ *   call in sub-blocks of `sub_block` <= block samples, `lds_bytes` of LDS each.
+ * process: ProcessInPlace (:244-248) of every channel, any n >= 0; results do
+ *   not depend on how a signal is cut into calls.  Host form: [channels][n].
+ *   Device form: rows of n at `stride` under the "Device buffers" contract,
+ *   asynchronous on `stream`; calls on different streams are serialised
+ *   through an event, as ad_fir's.
+ * reset: Reset (:189-197), ordered after the last call.                     */
+typedef struct ad_fdn ad_fdn;
+typedef struct ad_fdn_config {
+  double sample_rate, wet, dry, rt60_seconds, damp, pre_delay_seconds, mod_depth_seconds, mod_rate_hz;
+} ad_fdn_config;
+#define AD_FDN_SAMPLE_RATE 0 /* SetSampleRate :95 */
+#define AD_FDN_WET 1         /* SetWet :109 */
+#define AD_FDN_DRY 2         /* SetDry :120 */
+#define AD_FDN_RT60 3        /* SetRT60 :131 */
+#define AD_FDN_DAMP 4        /* SetDamp :143 */
+#define AD_FDN_PRE_DELAY 5   /* SetPreDelay :154 */
+#define AD_FDN_MOD_DEPTH 6   /* SetModDepth :166 */
+#define AD_FDN_MOD_RATE 7    /* SetModRate :178 */
+void ad_fdn_default_config(ad_fdn_config* cfg, double sample_rate);
+int ad_fdn_validate(const ad_fdn_config* cfg);
+int ad_fdn_create(const ad_fdn_config* cfg, int channels, int device, ad_fdn** out);
+int ad_fdn_set_param(ad_fdn* f, int which, double value);
+int ad_fdn_get_config(const ad_fdn* f, ad_fdn_config* cfg);
+int ad_fdn_derived(const ad_fdn* f, double feedback_gain[8], int64_t line_len[8], int64_t* pre_len,
+                   double* lfo_phase);
+int ad_fdn_kernel_info(const ad_fdn* f, int* block, int* sub_block, int* lds_bytes);
+int ad_fdn_process(ad_fdn* f, double* buf, int64_t n);
+int ad_fdn_process_device(ad_fdn* f, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_fdn_reset(ad_fdn* f);
+void ad_fdn_destroy(ad_fdn* f);
 
 /* ---- spectral correlation / deconvolution (dsp/conv/correlate.go,
  * dsp/conv/deconvolve.go) --------------------------------------
