@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "ad_common.hpp"
+#include "stream_order.hpp"
 #include "conv_kernels.hpp"
 #include "host_pipeline.hpp"
 #include "nupols_engine.hpp"
@@ -147,10 +148,8 @@ struct ad_conv {
 
   // multi-channel device calls: the engine's delay line and scratch are
   // shared by every caller stream, so a call on a new stream waits for the
-  // previous call's last launch (has_last: last may be the NULL stream)
-  hipStream_t last = nullptr;
-  bool has_last = false;
-  hipEvent_t done = nullptr;
+  // previous call's last launch
+  StreamOrder order;
 
   // partitioned: non-uniform multi-stage engine (64 <= latency <= 8192)
   std::unique_ptr<NupolsDev> nupd;
@@ -168,10 +167,7 @@ struct ad_conv {
     }
     gate_release(this);
     pipe.reset();
-    if (done) {
-      (void)hipEventSynchronize(done);
-      (void)hipEventDestroy(done);
-    }
+    order.release();  // after the pipeline, before the engines
     nupd.reset();
     eng.reset();
     if (stream) (void)hipStreamSynchronize(stream);
@@ -194,17 +190,6 @@ ad_conv* new_handle(Kind k, int device) {
     AD_FAIL(AD_ERR_DEVICE, "hipStreamCreate failed");
   }
   return h;
-}
-
-// Orders a device call on stream s after the handle's previous one.
-void order_after_last(ad_conv* h, hipStream_t s) {
-  if (!h->done) AD_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
-  if (h->has_last && h->last != s) AD_HIP(hipStreamWaitEvent(s, h->done, 0));
-}
-void mark_last(ad_conv* h, hipStream_t s) {
-  AD_HIP(hipEventRecord(h->done, s));
-  h->last = s;
-  h->has_last = true;
 }
 
 // Zero-latency streaming convolution state for blocks of B samples
@@ -484,9 +469,9 @@ void stream_convolve(ad_conv* h, const double* in, int64_t n, double* out) {
 void batch_convolve_multi(ad_conv* h, const double* const* in, int C, int64_t n, double* const* out,
                           int64_t out_len) {
   if (!h->pipe) h->pipe.reset(new HostPipeline(h->device));
-  order_after_last(h, h->stream);
+  h->order.enter(h->stream);
   h->pipe->offline(*h->eng, in, C, n, out, out_len, h->stream);
-  mark_last(h, h->stream);
+  h->order.leave(h->stream);
 }
 void batch_convolve(ad_conv* h, const double* in, int64_t n, double* out, int64_t out_len) {
   batch_convolve_multi(h, &in, 1, n, &out, out_len);
@@ -869,10 +854,10 @@ int ad_conv_reset(ad_conv* h) {
   return guard([&] {
     if (!h) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "nil handle");
     DeviceScope ds(h->device);
-    if (h->has_last) AD_HIP(hipStreamWaitEvent(h->stream, h->done, 0));  // after the last device call
+    h->order.join(h->stream);  // after the last device call
     if (h->nupd) h->nupd->reset(h->stream);
     stream_reset(h);
-    h->has_last = false;
+    h->order.clear();
   });
 }
 
@@ -1115,11 +1100,11 @@ int ad_conv_multi_process_device(ad_conv* h, const double* d_in, int64_t in_stri
     check_multi_rows(h, d_in, in_stride, in_len, d_out, out_stride, out_len);
     DeviceScope ds(h->device);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);  // NULL = the default (null) stream
-    order_after_last(h, s);
+    h->order.enter(s);
     h->eng->begin_offline(s);
     PipeCall pc(h->eng.get());
     h->eng->run(d_in, in_stride, in_len, d_out, out_stride, out_len, /*use_hist=*/false, s);
-    mark_last(h, s);
+    h->order.leave(s);
     h->seg_next = -1;
   });
 }
@@ -1141,12 +1126,12 @@ int ad_conv_multi_process_device_segment(ad_conv* h, const double* d_in, int64_t
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "conv segment: segments must follow each other in order");
     DeviceScope ds(h->device);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    order_after_last(h, s);
+    h->order.enter(s);
     if (out_begin == 0) h->eng->begin_offline(s);
     PipeCall pc(h->eng.get());
     h->eng->run(d_in, in_stride, in_len, d_out, out_stride, out_len, /*use_hist=*/false, s, out_begin / L,
                 (out_end + L - 1) / L);
-    mark_last(h, s);
+    h->order.leave(s);
     h->seg_next = out_end < out_len ? out_end : -1;
   });
 }
@@ -1171,7 +1156,7 @@ int ad_conv_multi_process_device_mix(ad_conv* h, const double* d_in, int64_t in_
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "conv segment: segments must follow each other in order");
     DeviceScope ds(h->device);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    order_after_last(h, s);
+    h->order.enter(s);
     if (out_begin == 0) h->eng->begin_offline(s);
     const int64_t jb = out_begin / L, je = (out_end + L - 1) / L;
     PipeCall pc(h->eng.get());
@@ -1186,7 +1171,7 @@ int ad_conv_multi_process_device_mix(ad_conv* h, const double* d_in, int64_t in_
                      first_parity & 1, s);
       AD_HIP(hipGetLastError());
     }
-    mark_last(h, s);
+    h->order.leave(s);
     h->seg_next = out_end < out_len ? out_end : -1;
   });
 }
@@ -1313,9 +1298,9 @@ int ad_conv_multi_stream_process_block_device(ad_conv* h, const double* d_in, in
     if (in_stride < B || out_stride < B) AD_FAIL(AD_ERR_LENGTH_MISMATCH, "conv: stride shorter than the block");
     DeviceScope ds(h->device);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    order_after_last(h, s);
+    h->order.enter(s);
     multi_stream_run(h, d_in, in_stride, d_out, out_stride, s);
-    mark_last(h, s);
+    h->order.leave(s);
   });
 }
 
@@ -1349,14 +1334,14 @@ int ad_conv_multi_stream_process_block(ad_conv* h, const double* const* in, doub
     h->din.reserve(cnt);
     h->dout.reserve(cnt);
     hipStream_t s = h->stream;
-    order_after_last(h, s);
+    h->order.enter(s);
     const int workers = cnt >= ((size_t)1 << 16) ? 8 : 0;
     parallel_for(channels, [&](int64_t c) { std::memcpy(h->pin_in + c * n, in[c], (size_t)n * sizeof(double)); },
                  workers);
     AD_HIP(hipMemcpyAsync(h->din.p, h->pin_in, cnt * sizeof(double), hipMemcpyHostToDevice, s));
     multi_stream_run(h, h->din.p, n, h->dout.p, n, s);
     AD_HIP(hipMemcpyAsync(h->pin_out, h->dout.p, cnt * sizeof(double), hipMemcpyDeviceToHost, s));
-    mark_last(h, s);
+    h->order.leave(s);
     AD_HIP(hipStreamSynchronize(s));
     parallel_for(channels, [&](int64_t c) { std::memcpy(out[c], h->pin_out + c * n, (size_t)n * sizeof(double)); },
                  workers);
@@ -1423,9 +1408,9 @@ int ad_conv_pc_multi_process_device(ad_conv* h, const double* d_in, int64_t in_s
       AD_FAIL(AD_ERR_LENGTH_MISMATCH, "conv: bad buffer geometry");
     DeviceScope ds(h->device);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    order_after_last(h, s);
+    h->order.enter(s);
     h->nupd->process(d_in, in_stride, d_out, out_stride, n, /*mix=*/false, 1.0, 0.0, s);
-    mark_last(h, s);
+    h->order.leave(s);
   });
 }
 
@@ -1438,9 +1423,9 @@ int ad_conv_reverb_multi_process_device(ad_conv* h, double* d_buf, int64_t strid
     if (n < 0 || stride < n || !d_buf) AD_FAIL(AD_ERR_LENGTH_MISMATCH, "conv: bad buffer geometry");
     DeviceScope ds(h->device);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    order_after_last(h, s);
+    h->order.enter(s);
     h->nupd->process(d_buf, stride, d_buf, stride, n, /*mix=*/true, h->wet, h->dry, s);
-    mark_last(h, s);
+    h->order.leave(s);
   });
 }
 
@@ -1454,11 +1439,11 @@ int ad_conv_reverb_multi_process(ad_conv* h, double* buf, int64_t n) {
     const size_t cnt = (size_t)h->channels * n;
     h->din.reserve(cnt);
     hipStream_t s = h->stream;
-    order_after_last(h, s);
+    h->order.enter(s);
     AD_HIP(hipMemcpyAsync(h->din.p, buf, cnt * sizeof(double), hipMemcpyHostToDevice, s));
     h->nupd->process(h->din.p, n, h->din.p, n, n, /*mix=*/true, h->wet, h->dry, s);
     AD_HIP(hipMemcpyAsync(buf, h->din.p, cnt * sizeof(double), hipMemcpyDeviceToHost, s));
-    mark_last(h, s);
+    h->order.leave(s);
     AD_HIP(hipStreamSynchronize(s));
   });
 }

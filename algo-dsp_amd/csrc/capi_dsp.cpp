@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ad_common.hpp"
+#include "stream_order.hpp"
 #include "dsp_kernels.hpp"
 
 using namespace adsp;
@@ -151,8 +152,8 @@ struct ad_fx_chain {
   hipEvent_t ev[3][kFxSlots] = {};
   DevBuf<double> xT[kFxSlots], vT[kFxSlots], envT[kFxSlots], inT[kFxSlots], coT[kFxSlots];
   DevBuf<double> midT[kFxSlots];  // split K_eq: the first part's output rows
-  // EQ-only chains, one K_eq part per section (fx_run_staged): section k's
-  // output rows of chunk c in secT[k][c & 1], read by section k + 1 one launch later
+  // one K_eq part per section (FxPlan::PerSection): section k's output rows
+  // of chunk c in secT[k][c & 1], read by section k + 1 one launch later
   DevBuf<double> secT[kMaxSecPerPass][2];
   DevBuf<double> lane_dump;  // K_lanes: the stores outside the signal (kFxEqLaneDump doubles)
   // time-parallel engine (fx_tp.hip): K_eq segment states
@@ -286,46 +287,44 @@ bool fx_staged_ok(const ad_fx_chain* h) {
          (h->nsec > 0 || h->comp_on || h->verb_on);
 }
 
-// Split K_eq (sections 0 .. s1-1 of chunk i beside the rest + the detector of
-// chunk i - 1, one launch): the EQ recurrences of a channel group run on two
-// CUs, every wave on a SIMD of its own.  Returns s1, or 0 for one pipeline.
-int fx_eq_split(const ad_fx_chain* h) {
-  if (h->engine == AD_FX_ENGINE_STAGED_NOSPLIT) return 0;
-  if (!h->comp_on || h->nsec < 3) return 0;
-  return (h->nsec + 2) / 2;  // part waves (s1 + loader) vs (ns - s1 + detector + loader)
-}
-
-// EQ-only chains (no compressor) run one K_eq part per section (see
-// fx_run_staged); STAGED_NOSPLIT keeps the one-workgroup pipeline.
-#ifndef AD_FX_EQ_PER_SECTION  // tools/ A/B builds
-#define AD_FX_EQ_PER_SECTION 1
-#endif
-#ifndef AD_FX_EQ_PER_SECTION_MAXCH
-// above this many channels the one-workgroup-per-group kernel fills the chip and
-// wins (tools/eq_cross.py, profiles/r05_eq_cross.txt: per-section / whole-chain
-// Msamples/s at 4096 ch 39.4 / 38.2, 8192 ch 44.9 / 60.7, 16384 ch 47.9 / 85.2)
-#define AD_FX_EQ_PER_SECTION_MAXCH 4096
-#endif
-// EQ-only chains without Freeverb run K_lanes (fx_eq_lanes.hip): the sections
-// across the lanes of a DPP row, one launch over the whole call, in place on
-// the user buffer (no transposes, no chunks).
-#ifndef AD_FX_EQ_LANES  // tools/ A/B builds
-#define AD_FX_EQ_LANES 1
-#endif
-#ifndef AD_FX_EQ_LANES_MAXCH
+// Which kernel runs the EQ of a staged call (fx_run_staged).
+enum class FxPlan {
+  // K_lanes (fx_eq_lanes.hip): the sections across the lanes of a DPP row, one
+  // launch over the whole call, in place on the user buffer (no transposes, no
+  // chunks)
+  Lanes,
+  // one K_eq part per section, each a workgroup of its own, a pipeline over
+  // the chunks (launch_fx_eq_sec)
+  PerSection,
+  // split K_eq (sections 0 .. s1-1 of chunk i beside the rest + the detector of
+  // chunk i - 1, one launch): the EQ recurrences of a channel group run on two
+  // CUs, every wave on a SIMD of its own
+  Split,
+  // one K_eq pipeline per channel group (what STAGED_NOSPLIT asks for)
+  WholeChain,
+};
 // above this many channels the one-workgroup-per-channel-group kernel fills
-// the chip and wins (tools/eq_lanes_bench.py: 8192 ch 69.6 / 60.2, 16384 ch
-// 79.1 / 84.8 Gsamples/s, lanes / one workgroup per group)
-#define AD_FX_EQ_LANES_MAXCH 8192
-#endif
-bool fx_eq_lanes(const ad_fx_chain* h) {
-  return AD_FX_EQ_LANES && h->engine != AD_FX_ENGINE_STAGED_NOSPLIT && !h->comp_on && !h->verb_on && h->nsec >= 1 &&
-         h->nsec <= kMaxSecPerPass && h->channels <= AD_FX_EQ_LANES_MAXCH;
-}
+// the chip and wins over K_lanes (tools/eq_lanes_bench.py: 8192 ch 69.6 / 60.2,
+// 16384 ch 79.1 / 84.8 Gsamples/s, lanes / one workgroup per group)
+constexpr int kFxEqLanesMaxCh = 8192;
+// above this many (padded) channels the one-workgroup-per-group kernel fills the
+// chip and wins over one part per section (tools/eq_cross.py,
+// profiles/r05_eq_cross.txt: per-section / whole-chain Msamples/s at 4096 ch
+// 39.4 / 38.2, 8192 ch 44.9 / 60.7, 16384 ch 47.9 / 85.2)
+constexpr int kFxEqPerSectionMaxCh = 4096;
 
-bool fx_eq_per_section(const ad_fx_chain* h) {
-  return AD_FX_EQ_PER_SECTION && h->engine != AD_FX_ENGINE_STAGED_NOSPLIT && !h->comp_on && h->nsec >= 2 &&
-         h->nsec <= kMaxSecPerPass && h->cpad <= AD_FX_EQ_PER_SECTION_MAXCH;
+// The plan of a chain that fx_staged_ok accepts (so nsec <= kMaxSecPerPass).
+// Chains without a compressor: EQ-only chains up to kFxEqLanesMaxCh channels
+// run K_lanes; the per-section pipeline runs EQ (two sections or more) +
+// Freeverb chains up to kFxEqPerSectionMaxCh padded channels, and nothing
+// else: without Freeverb such a chain is within K_lanes' range and goes there.
+// With a compressor, three sections or more split the EQ/detector stage.
+FxPlan fx_staged_plan(const ad_fx_chain* h) {
+  if (h->engine == AD_FX_ENGINE_STAGED_NOSPLIT) return FxPlan::WholeChain;
+  if (h->comp_on) return h->nsec >= 3 ? FxPlan::Split : FxPlan::WholeChain;
+  if (!h->verb_on && h->nsec >= 1 && h->channels <= kFxEqLanesMaxCh) return FxPlan::Lanes;
+  if (h->verb_on && h->nsec >= 2 && h->cpad <= kFxEqPerSectionMaxCh) return FxPlan::PerSection;
+  return FxPlan::WholeChain;
 }
 
 constexpr int64_t kFxChunk = 16384;  // staged engine: samples per stage chunk
@@ -357,9 +356,97 @@ void fx_grow_tmax(ad_fx_chain* h, int64_t t) {
   h->tmax = t;
 }
 
-void fx_run_staged(ad_fx_chain* h, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
+// The stage streams and the per-slot events of both chunked engines.
+void fx_streams_init(ad_fx_chain* h) {
+  if (h->st[0]) return;
+  for (auto& x : h->st) AD_HIP(lib_stream_create(&x));
+  for (auto& e2 : h->ev)
+    for (auto& e : e2) AD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  AD_HIP(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
+}
+
+// Per-slot events, ev[.][slot]: the chunk's EQ (time-parallel with compressor
+// + Freeverb: its gain) is done; its combs (staged) or its detector
+// (time-parallel) are done; its allpasses / reverb / output, the slot's last
+// reader, are done.
+enum { EE = 0, EC = 1, ED = 1, EA = 2 };
+
+// The buffers a call of an engine indexes and the doubles each must hold.
+struct FxWants {
+  struct Want {
+    DevBuf<double>* b;
+    size_t n;
+  } w[kFxSlots * 6 + 2 * kMaxSecPerPass + 4];
+  int cnt = 0;
+  void add(DevBuf<double>& b, size_t n) { w[cnt++] = Want{&b, n}; }
+};
+
+// Rows of a chunk buffer: every buffer a kernel indexes at row stride tmax
+// must hold cpad * tmax doubles.
+size_t fx_rows(const ad_fx_chain* h, int64_t T) { return (size_t)h->cpad * std::max(T, h->tmax); }
+
+// Sizes an engine's buffers for chunks of T samples.  tmax is shared by both
+// engines, and either may have raised it without sizing the other's buffers,
+// so each buffer's own capacity is checked, not tmax.  Only when something
+// must grow: wait until no stage is running (st[] and the caller's stream),
+// then raise tmax and reserve.  No buffer is released or reallocated
+// without that wait before it.
+void fx_size_buffers(ad_fx_chain* h, int64_t T, hipStream_t s, const FxWants& ws) {
+  bool grow = T > h->tmax;
+  for (int i = 0; i < ws.cnt && !grow; ++i) grow = !ws.w[i].b->p || ws.w[i].b->n < ws.w[i].n;
+  if (!grow) return;
+  for (hipStream_t x : h->st) AD_HIP(hipStreamSynchronize(x));
+  AD_HIP(hipStreamSynchronize(s));
+  fx_grow_tmax(h, std::max(T, h->tmax));
+  for (int i = 0; i < ws.cnt; ++i) ws.w[i].b->reserve(ws.w[i].n);
+}
+
+// Chunk ci (T samples, the last one shorter) of a call on (d_buf, stride, n):
+// its stage arguments, on the buffers of slot ci % kFxSlots.
+FxStageArgs fx_chunk_args(const ad_fx_chain* h, double* d_buf, int64_t stride, int64_t n, int64_t T, int64_t ci) {
+  const int ks = (int)(ci % kFxSlots);
+  const int64_t t0 = ci * T;
+  FxStageArgs a{};
+  a.channels = h->channels;
+  a.cpad = h->cpad;
+  a.len = std::min(T, n - t0);
+  a.buf = d_buf + t0;
+  a.stride = stride;
+  a.xT = h->xT[ks].p;
+  a.vT = h->vT[ks].p;
+  a.envT = h->envT[ks].p;
+  a.inT = h->inT[ks].p;
+  a.coT = h->coT[ks].p;
+  a.tmax = h->tmax;
+  a.eq.nsec = h->nsec;
+  a.eq.sec = h->sec_dev.p;
+  a.eq.sec_ch_stride = h->eq_uniform ? 0 : (int64_t)h->nsec * kSecStride;
+  a.eq.state = h->eq_state.p;
+  a.cp = h->cp;
+  a.cs = h->cs.p;
+  a.rms_ring = h->ring.p;
+  a.vp = h->vp;
+  a.vs = h->vs.p;
+  a.vbuf = h->vbuf.p;
+  return a;
+}
+
+// The Freeverb of a staged chunk (slot k) behind its EQ / gain on s: the combs
+// on st[0], the allpasses on st[1], each stage's end in the slot's events.
+void fx_verb_tail(ad_fx_chain* h, const FxStageArgs& a, int k, hipStream_t s) {
+  hipStream_t sc = h->st[0], sa = h->st[1];
+  AD_HIP(hipEventRecord(h->ev[EE][k], s));
+  AD_HIP(hipStreamWaitEvent(sc, h->ev[EE][k], 0));
+  launch_fx_comb(a, sc);
+  AD_HIP(hipEventRecord(h->ev[EC][k], sc));
+  AD_HIP(hipStreamWaitEvent(sa, h->ev[EC][k], 0));
+  launch_fx_allpass(a, sa);
+  AD_HIP(hipEventRecord(h->ev[EA][k], sa));
+}
+
+void fx_run_staged(ad_fx_chain* h, FxPlan plan, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
   const bool eq = h->nsec > 0, comp = h->comp_on, verb = h->verb_on;
-  if (fx_eq_lanes(h)) {
+  if (plan == FxPlan::Lanes) {
     if (!h->lane_dump.p) h->lane_dump.alloc(kFxEqLaneDump);
     FxEqLaneArgs a{};
     a.buf = d_buf;
@@ -383,99 +470,54 @@ void fx_run_staged(ad_fx_chain* h, double* d_buf, int64_t stride, int64_t n, hip
     return;
   }
   const int64_t T = std::min(h->chunk > 0 ? h->chunk : kFxChunk, n);
-  if (!h->st[0]) {
-    for (auto& x : h->st) AD_HIP(lib_stream_create(&x));
-    for (auto& e2 : h->ev)
-      for (auto& e : e2) AD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    AD_HIP(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-  }
-  const bool need_x = eq || comp, need_v = comp || (eq && !verb);
-  const int s1 = fx_eq_split(h);
+  const int64_t nch = (n + T - 1) / T;
+  fx_streams_init(h);
+  // split K_eq: sections 0 .. s1-1 in the first part; part waves (s1 + loader)
+  // vs (ns - s1 + detector + loader)
+  const int s1 = plan == FxPlan::Split ? (h->nsec + 2) / 2 : 0;
   {
-    // Every buffer a kernel indexes at row stride tmax must hold cpad * tmax
-    // rows: tmax is shared with the time-parallel engine, which may have
-    // raised it without sizing this engine's buffers (each buffer's own
-    // capacity is checked, not tmax).
-    const size_t r = (size_t)h->cpad * std::max(T, h->tmax);
-    auto shortb = [](const DevBuf<double>& b, size_t want) { return !b.p || b.n < want; };
-    bool grow = false;
-    for (int k = 0; k < kFxSlots; ++k)
-      grow = grow || (need_x && shortb(h->xT[k], r)) || (need_v && shortb(h->vT[k], r)) ||
-             (comp && shortb(h->envT[k], r)) || (verb && (shortb(h->inT[k], r) || shortb(h->coT[k], r * kVerbCombs))) ||
-             (s1 && shortb(h->midT[k], r));
-    if (grow || T > h->tmax) {  // (re)size the chunk buffers once no stage is running
-      for (hipStream_t x : h->st) AD_HIP(hipStreamSynchronize(x));
-      AD_HIP(hipStreamSynchronize(s));
-      fx_grow_tmax(h, std::max(T, h->tmax));
-      for (int k = 0; k < kFxSlots; ++k) {
-        if (need_x) h->xT[k].reserve(r);
-        if (need_v) h->vT[k].reserve(r);
-        if (comp) h->envT[k].reserve(r);
-        if (verb) {
-          h->inT[k].reserve(r);
-          h->coT[k].reserve(r * kVerbCombs);
-        }
-        if (s1) h->midT[k].reserve(r);
+    const bool need_x = eq || comp, need_v = comp || (eq && !verb);
+    const size_t r = fx_rows(h, T);
+    FxWants w;
+    for (int k = 0; k < kFxSlots; ++k) {
+      if (need_x) w.add(h->xT[k], r);
+      if (need_v) w.add(h->vT[k], r);
+      if (comp) w.add(h->envT[k], r);
+      if (verb) {
+        w.add(h->inT[k], r);
+        w.add(h->coT[k], r * kVerbCombs);
       }
+      if (s1) w.add(h->midT[k], r);
     }
+    if (plan == FxPlan::PerSection)
+      for (int k = 0; k + 1 < h->nsec; ++k)
+        for (auto& b : h->secT[k]) w.add(b, r);
+    fx_size_buffers(h, T, s, w);
   }
   // stage streams: the caller's stream runs input transpose + EQ/detector +
   // gain; st[0] the combs, st[1] the allpasses (three queues in all)
-  hipStream_t sc = h->st[0], sa = h->st[1];
-  enum { EE = 0, EC = 1, EA = 2 };
   if (verb) {
     AD_HIP(hipEventRecord(h->ev_in, s));
-    AD_HIP(hipStreamWaitEvent(sc, h->ev_in, 0));
-    AD_HIP(hipStreamWaitEvent(sa, h->ev_in, 0));
+    AD_HIP(hipStreamWaitEvent(h->st[0], h->ev_in, 0));
+    AD_HIP(hipStreamWaitEvent(h->st[1], h->ev_in, 0));
   }
-  // chunk i's stage arguments (slot i % kFxSlots)
-  auto chunk_args = [&](int64_t ci) {
-    const int ks = (int)(ci % kFxSlots);
-    const int64_t t0 = ci * T;
-    FxStageArgs a{};
-    a.channels = h->channels;
-    a.cpad = h->cpad;
-    a.len = std::min(T, n - t0);
-    a.buf = d_buf + t0;
-    a.stride = stride;
-    a.xT = h->xT[ks].p;
-    a.vT = h->vT[ks].p;
-    a.envT = h->envT[ks].p;
-    a.inT = h->inT[ks].p;
-    a.coT = h->coT[ks].p;
-    a.tmax = h->tmax;
-    a.eq.nsec = h->nsec;
-    a.eq.sec = h->sec_dev.p;
-    a.eq.sec_ch_stride = h->eq_uniform ? 0 : (int64_t)h->nsec * kSecStride;
-    a.eq.state = h->eq_state.p;
-    a.cp = h->cp;
-    a.cs = h->cs.p;
-    a.rms_ring = h->ring.p;
-    a.vp = h->vp;
-    a.vs = h->vs.p;
-    a.vbuf = h->vbuf.p;
-    return a;
-  };
-  if (fx_eq_per_section(h)) {
-    // EQ-only chain (a12-a14), one K_eq part per section: launch i runs section
+  auto chunk_args = [&](int64_t ci) { return fx_chunk_args(h, d_buf, stride, n, T, ci); };
+  int kl = 0;  // the last chunk's slot
+  if (plan == FxPlan::PerSection) {
+    // EQ + Freeverb chain, one K_eq part per section: launch i runs section
     // k of chunk i - k for every k, each part a workgroup of its own (one
     // section wave and a loader: the section has a SIMD and a CU to itself),
     // reading section k - 1's rows of that chunk, which the previous launch
-    // wrote into secT[k - 1][chunk & 1]; the last section writes vT (inT with
-    // Freeverb), and that chunk's later stages follow the launch.  The bits
-    // are the single-part kernel's: every section runs the reference
-    // operations on the same samples, its state carried across chunks.
+    // wrote into secT[k - 1][chunk & 1]; the last section writes inT, and that
+    // chunk's Freeverb follows the launch.  The bits are the single-part
+    // kernel's: every section runs the reference operations on the same
+    // samples, its state carried across chunks.
     const int ns = h->nsec;
-    const size_t r = (size_t)h->cpad * std::max(T, h->tmax);
-    for (int k = 0; k + 1 < ns; ++k)
-      for (auto& b : h->secT[k]) b.reserve(r);
-    const int64_t nch = (n + T - 1) / T;
-    int kl = 0;
     for (int64_t li = 0; li < nch + ns - 1; ++li) {
       const int64_t cd = li - (ns - 1);  // the chunk whose last section runs in this launch
       if (li < nch) launch_fx_transpose_in(chunk_args(li), chunk_args(li).xT, s);
       // inT / coT of slot cd % kFxSlots: chunk cd - kFxSlots's allpasses are done
-      if (verb && cd >= kFxSlots) AD_HIP(hipStreamWaitEvent(s, h->ev[EA][cd % kFxSlots], 0));
+      if (cd >= kFxSlots) AD_HIP(hipStreamWaitEvent(s, h->ev[EA][cd % kFxSlots], 0));
       FxStageArgs e = chunk_args(std::min(li, nch - 1));
       e.nparts = 0;
       for (int k = 0; k < ns; ++k) {
@@ -483,37 +525,20 @@ void fx_run_staged(ad_fx_chain* h, double* d_buf, int64_t stride, int64_t n, hip
         if (c < 0 || c >= nch) continue;
         const FxStageArgs ac = chunk_args(c);
         const double* in = k == 0 ? ac.xT : h->secT[k - 1][c & 1].p;
-        double* out = k == ns - 1 ? (verb ? ac.inT : ac.vT) : h->secT[k][c & 1].p;
+        double* out = k == ns - 1 ? ac.inT : h->secT[k][c & 1].p;
         e.part[e.nparts++] = FxEqPart{k, 1, 0, ac.len, in, out, nullptr};
       }
       launch_fx_eq_sec(e, s);
       if (cd < 0) continue;
-      const FxStageArgs b = chunk_args(cd);
-      if (!verb) {
-        launch_fx_transpose_out(b, b.vT, s);
-        continue;
-      }
       kl = (int)(cd % kFxSlots);
-      AD_HIP(hipEventRecord(h->ev[EE][kl], s));
-      AD_HIP(hipStreamWaitEvent(sc, h->ev[EE][kl], 0));
-      launch_fx_comb(b, sc);
-      AD_HIP(hipEventRecord(h->ev[EC][kl], sc));
-      AD_HIP(hipStreamWaitEvent(sa, h->ev[EC][kl], 0));
-      launch_fx_allpass(b, sa);
-      AD_HIP(hipEventRecord(h->ev[EA][kl], sa));
+      fx_verb_tail(h, chunk_args(cd), kl, s);
     }
-    AD_HIP(hipGetLastError());
-    if (verb) AD_HIP(hipStreamWaitEvent(s, h->ev[EA][kl], 0));
-    return;
-  }
-  if (s1) {
+  } else if (plan == FxPlan::Split) {
     // Split K_eq: launch i runs part A (sections 0 .. s1-1) of chunk i and
     // part B (sections s1 .. ns-1 + detector) of chunk i - 1, which read A's
     // rows of chunk i - 1 from midT; chunk i - 1's later stages follow.  A
     // slot is rewritten (transpose / part A of chunk i) only after chunk
     // i - kFxSlots's allpasses, enqueued kFxSlots - 1 iterations earlier.
-    const int64_t nch = (n + T - 1) / T;
-    int kl = 0;
     for (int64_t ci = 0; ci <= nch; ++ci) {
       FxStageArgs e{};
       if (ci < nch) {
@@ -531,73 +556,32 @@ void fx_run_staged(ad_fx_chain* h, double* d_buf, int64_t stride, int64_t n, hip
         if (ci == 1) e.prof = fx_prof_begin(h, kFxProfWords, s);
         launch_fx_eq_parts(e, s);
         launch_fx_gain(b, !verb, s);
-        if (verb) {
-          kl = (int)((ci - 1) % kFxSlots);
-          AD_HIP(hipEventRecord(h->ev[EE][kl], s));
-          AD_HIP(hipStreamWaitEvent(sc, h->ev[EE][kl], 0));
-          launch_fx_comb(b, sc);
-          AD_HIP(hipEventRecord(h->ev[EC][kl], sc));
-          AD_HIP(hipStreamWaitEvent(sa, h->ev[EC][kl], 0));
-          launch_fx_allpass(b, sa);
-          AD_HIP(hipEventRecord(h->ev[EA][kl], sa));
-        }
+        kl = (int)((ci - 1) % kFxSlots);
+        if (verb) fx_verb_tail(h, b, kl, s);
       } else {
         launch_fx_eq_parts(e, s);
       }
     }
-    AD_HIP(hipGetLastError());
-    if (verb) AD_HIP(hipStreamWaitEvent(s, h->ev[EA][kl], 0));
-    return;
-  }
-  int64_t i = 0;
-  int k = 0;
-  for (int64_t t0 = 0; t0 < n; t0 += T, ++i) {
-    k = (int)(i % kFxSlots);
-    const bool reuse = i >= kFxSlots;  // slot k was used by chunk i - kFxSlots
-    FxStageArgs a{};
-    a.channels = h->channels;
-    a.cpad = h->cpad;
-    a.len = std::min(T, n - t0);
-    a.buf = d_buf + t0;
-    a.stride = stride;
-    a.xT = h->xT[k].p;
-    a.vT = h->vT[k].p;
-    a.envT = h->envT[k].p;
-    a.inT = h->inT[k].p;
-    a.coT = h->coT[k].p;
-    a.tmax = h->tmax;
-    a.eq.nsec = h->nsec;
-    a.eq.sec = h->sec_dev.p;
-    a.eq.sec_ch_stride = h->eq_uniform ? 0 : (int64_t)h->nsec * kSecStride;
-    a.eq.state = h->eq_state.p;
-    a.cp = h->cp;
-    a.cs = h->cs.p;
-    a.rms_ring = h->ring.p;
-    a.vp = h->vp;
-    a.vs = h->vs.p;
-    a.vbuf = h->vbuf.p;
-    if (i == 0) a.prof = fx_prof_begin(h, kFxProfWords, s);
-    if (verb && reuse) AD_HIP(hipStreamWaitEvent(s, h->ev[EA][k], 0));  // inT / coT of that chunk consumed
-    if (eq || comp) {
-      launch_fx_transpose_in(a, a.xT, s);
-      launch_fx_eq(a, comp, (verb && !comp) ? kFxOutInT : kFxOutVT, s);
-      if (comp) launch_fx_gain(a, !verb, s);
-      if (!comp && !verb) launch_fx_transpose_out(a, a.vT, s);
-    } else {
-      launch_fx_transpose_in(a, a.inT, s);
-    }
-    if (verb) {
-      AD_HIP(hipEventRecord(h->ev[EE][k], s));
-      AD_HIP(hipStreamWaitEvent(sc, h->ev[EE][k], 0));
-      launch_fx_comb(a, sc);
-      AD_HIP(hipEventRecord(h->ev[EC][k], sc));
-      AD_HIP(hipStreamWaitEvent(sa, h->ev[EC][k], 0));
-      launch_fx_allpass(a, sa);
-      AD_HIP(hipEventRecord(h->ev[EA][k], sa));
+  } else {
+    for (int64_t i = 0; i < nch; ++i) {
+      kl = (int)(i % kFxSlots);
+      FxStageArgs a = chunk_args(i);
+      if (i == 0) a.prof = fx_prof_begin(h, kFxProfWords, s);
+      // slot kl was used by chunk i - kFxSlots: its inT / coT are consumed
+      if (verb && i >= kFxSlots) AD_HIP(hipStreamWaitEvent(s, h->ev[EA][kl], 0));
+      if (eq || comp) {
+        launch_fx_transpose_in(a, a.xT, s);
+        launch_fx_eq(a, comp, (verb && !comp) ? kFxOutInT : kFxOutVT, s);
+        if (comp) launch_fx_gain(a, !verb, s);
+        if (!comp && !verb) launch_fx_transpose_out(a, a.vT, s);
+      } else {
+        launch_fx_transpose_in(a, a.inT, s);
+      }
+      if (verb) fx_verb_tail(h, a, kl, s);
     }
   }
   AD_HIP(hipGetLastError());
-  if (verb) AD_HIP(hipStreamWaitEvent(s, h->ev[EA][k], 0));  // the last chunk's allpasses follow all work
+  if (verb) AD_HIP(hipStreamWaitEvent(s, h->ev[EA][kl], 0));  // the last chunk's allpasses follow all work
 }
 
 // The EQ's round-off noise relative to its signal, as the time-parallel
@@ -634,24 +618,14 @@ double fx_eq_noise(const std::vector<double>& tab, int sets, int nsec) {
 
 // The time-parallel engine (fx_tp.hip): per chunk of T samples, the caller's
 // stream runs the input transpose and the three EQ launches (K_eqz, K_carry,
-// K_eqx); st[0] the detector (serial per channel) and the gain of that chunk;
-// st[1] the reverb.  So chunk i's EQ overlaps chunk i-1's detector and chunk
-// i-2's reverb.  A slot is reused only after st[1] is done with it (the
-// detector and the gain precede st[1]'s work on every chunk).
-#ifndef AD_FX_TP_CHUNK  // tools/ A/B builds only
-#define AD_FX_TP_CHUNK 49152  // config 5 (tools/fx_chunk_sweep.py, round 5 schedule + 64-row detector batches): 24576 11.7, 32768 12.3-12.4, 49152 12.5-12.6, 65536 12.4-12.5 Gsamples/s
-#endif
-constexpr int64_t kFxTpChunk = AD_FX_TP_CHUNK;
-#ifndef AD_FX_TP_SERIAL_TAIL  // tools/ A/B builds
-#define AD_FX_TP_SERIAL_TAIL 0
-#endif
-constexpr bool kFxTpSerialTail = AD_FX_TP_SERIAL_TAIL;  // gain + Freeverb on the caller's stream (fx_run_tp)
-#ifndef AD_FX_TP_GAIN_ON_S  // tools/ A/B builds
-#define AD_FX_TP_GAIN_ON_S 1
-#endif
-// chunk i - 1's gain on the caller's stream behind chunk i's EQ, its Freeverb on
-// st[1] after it: the detector's stream runs detectors back to back (fx_run_tp)
-constexpr bool kFxTpGainOnS = AD_FX_TP_GAIN_ON_S;
+// K_eqx); st[0] the detector (serial per channel) of that chunk; st[1] the
+// reverb.  So chunk i's EQ overlaps chunk i-1's detector and chunk i-2's
+// reverb.  A slot is reused only after st[1] is done with it (the detector
+// and the gain precede st[1]'s work on every chunk).
+// The default chunk, config 5 (tools/fx_chunk_sweep.py, round 5 schedule +
+// 64-row detector batches): 24576 11.7, 32768 12.3-12.4, 49152 12.5-12.6,
+// 65536 12.4-12.5 Gsamples/s; ad_fx_chain_set_engine's chunk overrides it.
+constexpr int64_t kFxTpChunk = 49152;
 constexpr int kFxTpSeg = 64;     // K_eq segment (samples), at least
 constexpr size_t kFxTpMatsCached = 8;  // segment lengths whose maps stay cached
 
@@ -759,45 +733,28 @@ int fx_comb_warmup(const VerbParams& vp) {
 void fx_run_tp(ad_fx_chain* h, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
   const bool eq = h->nsec > 0, comp = h->comp_on, verb = h->verb_on;
   const int64_t T = std::min(h->chunk > 0 ? h->chunk : kFxTpChunk, n);
-  if (!h->st[0]) {
-    for (auto& x : h->st) AD_HIP(lib_stream_create(&x));
-    for (auto& e2 : h->ev)
-      for (auto& e : e2) AD_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    AD_HIP(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-  }
+  fx_streams_init(h);
   {
-    // each buffer's own capacity against cpad * tmax (tmax is shared with the
-    // staged engine, which may have raised it; see fx_run_staged)
-    const size_t r = (size_t)h->cpad * std::max(T, h->tmax);
-    auto shortb = [](const DevBuf<double>& b, size_t want) { return !b.p || b.n < want; };
-    bool grow = (verb && shortb(h->coC, (size_t)h->channels * 2 * kVerbCombs * kFxVerbSB)) ||
-                (eq && shortb(h->tp_zs, (size_t)kFxTpMaxSeg * h->nsec * h->cpad * 2));
-    for (int k = 0; k < kFxSlots; ++k)
-      grow = grow || shortb(h->xT[k], r) || (eq && shortb(h->vT[k], r)) || (comp && shortb(h->envT[k], r)) ||
-             (comp && verb && shortb(h->inC[k], r));
-    if (grow || T > h->tmax) {  // (re)size once no stage is running
-      for (hipStream_t x : h->st) AD_HIP(hipStreamSynchronize(x));
-      AD_HIP(hipStreamSynchronize(s));
-      fx_grow_tmax(h, std::max(T, h->tmax));
-      for (int k = 0; k < kFxSlots; ++k) {
-        h->xT[k].reserve(r);
-        if (eq) h->vT[k].reserve(r);
-        if (comp) h->envT[k].reserve(r);
-        if (comp && verb) h->inC[k].reserve(r);
-      }
-      if (verb) h->coC.reserve((size_t)h->channels * 2 * kVerbCombs * kFxVerbSB);  // two halves (k_fxtp_verb_pipe)
-      if (eq) {
-        h->tp_zs.reserve((size_t)kFxTpMaxSeg * h->nsec * h->cpad * 2);
-        h->tp_carry.reserve((size_t)kFxTpMaxSeg * h->nsec * h->cpad * 4);
-      }
+    const size_t r = fx_rows(h, T);
+    FxWants w;
+    for (int k = 0; k < kFxSlots; ++k) {
+      w.add(h->xT[k], r);
+      if (eq) w.add(h->vT[k], r);
+      if (comp) w.add(h->envT[k], r);
+      if (comp && verb) w.add(h->inC[k], r);
     }
+    if (verb) w.add(h->coC, (size_t)h->channels * 2 * kVerbCombs * kFxVerbSB);  // two halves (k_fxtp_verb_pipe)
+    if (eq) {
+      w.add(h->tp_zs, (size_t)kFxTpMaxSeg * h->nsec * h->cpad * 2);
+      w.add(h->tp_carry, (size_t)kFxTpMaxSeg * h->nsec * h->cpad * 4);
+    }
+    fx_size_buffers(h, T, s, w);
   }
 #ifdef AD_FX_TP_SERIAL  // tools/ builds only: every stage on the caller's stream (isolated kernel times)
   hipStream_t sd = s, sv = s;
 #else
   hipStream_t sd = h->st[0], sv = h->st[1];
 #endif
-  enum { EE = 0, ED = 1, EA = 2 };
   if (verb && !h->verb_cm) {  // the delay lines into K_verb's channel-major layout
     h->vbufC.reserve((size_t)kVerbLen * h->channels);
     launch_vbuf_layout(h->vbuf.p, h->vbufC.p, h->cpad, h->channels, true, s);
@@ -807,26 +764,15 @@ void fx_run_tp(ad_fx_chain* h, double* d_buf, int64_t stride, int64_t n, hipStre
   AD_HIP(hipStreamWaitEvent(sd, h->ev_in, 0));
   AD_HIP(hipStreamWaitEvent(sv, h->ev_in, 0));
   const int wu = verb ? fx_comb_warmup(h->vp) : 0;
-  // kFxTpSerialTail: the gain + Freeverb of a chunk on the caller's stream
-  // (see the loop); slot reuse then follows from that stream's order: chunk i's
-  // transpose and EQ come after chunk i - 1's (and so i - kFxSlots's) tail,
-  // whose wait on the detector orders every reader of the slot before them
+  // Compressor + Freeverb: chunk i - 1's gain on s (it waits there for its
+  // detector, by then chunk i's EQ is queued ahead of it) and its Freeverb on
+  // sv behind the gain, so the detector's stream runs detectors back to back;
+  // EE[kp] is re-recorded after the gain (the detector's wait on the EQ's
+  // record was already enqueued).  inC[kp]'s previous reader, chunk
+  // i - 1 - kFxSlots's Freeverb, is ordered before the gain by s's own wait on
+  // that slot at the top of the loop; on CU-masked streams of their own, the
+  // detector and the gain measured 2x slower.
   FxStageArgs prev{};
-  auto tail = [&](const FxStageArgs& p, int kp) {
-    AD_HIP(hipStreamWaitEvent(s, h->ev[ED][kp], 0));
-    FxStageArgs b = p;
-    b.buf = h->inC[kp].p;
-    b.stride = h->tmax;
-    launch_fx_gain(b, true, s);
-    launch_fxtp_verb(p, h->inC[kp].p, h->tmax, h->vbufC.p, h->coC.p, wu, s);
-  };
-  // kFxTpGainOnS: chunk i - 1's gain on s (it waits there for its detector,
-  // by then chunk i's EQ is queued ahead of it) and its Freeverb on sv behind
-  // the gain; EE[kp] is re-recorded after the gain (the detector's wait on the
-  // EQ's record was already enqueued)
-  // (inC[kp]'s previous reader, chunk i - 1 - kFxSlots's Freeverb, is ordered
-  // before the gain by s's own wait on that slot at the top of the loop; on
-  // CU-masked streams of their own, the detector and the gain measured 2x slower)
   auto gain_verb = [&](const FxStageArgs& p, int kp) {
     AD_HIP(hipStreamWaitEvent(s, h->ev[ED][kp], 0));
     FxStageArgs b = p;
@@ -838,34 +784,15 @@ void fx_run_tp(ad_fx_chain* h, double* d_buf, int64_t stride, int64_t n, hipStre
     launch_fxtp_verb(p, h->inC[kp].p, h->tmax, h->vbufC.p, h->coC.p, wu, sv, true);
     AD_HIP(hipEventRecord(h->ev[EA][kp], sv));
   };
-  const bool gain_on_s = kFxTpGainOnS && !kFxTpSerialTail && comp && verb;
-  int64_t i = 0;
+  const int64_t nch = (n + T - 1) / T;
   int k = 0;
-  for (int64_t t0 = 0; t0 < n; t0 += T, ++i) {
+  for (int64_t i = 0; i < nch; ++i) {
     k = (int)(i % kFxSlots);
-    FxStageArgs a{};
-    a.channels = h->channels;
-    a.cpad = h->cpad;
-    a.len = std::min(T, n - t0);
-    a.buf = d_buf + t0;
-    a.stride = stride;
-    a.xT = h->xT[k].p;
-    a.vT = eq ? h->vT[k].p : h->xT[k].p;  // the EQ output (or the input)
-    a.envT = h->envT[k].p;
-    a.inT = nullptr;
-    a.tmax = h->tmax;
-    a.eq.nsec = h->nsec;
-    a.eq.sec = h->sec_dev.p;
-    a.eq.sec_ch_stride = h->eq_uniform ? 0 : (int64_t)h->nsec * kSecStride;
-    a.eq.state = h->eq_state.p;
-    a.cp = h->cp;
-    a.cs = h->cs.p;
-    a.rms_ring = h->ring.p;
-    a.vp = h->vp;
-    a.vs = h->vs.p;
-    a.vbuf = h->vbuf.p;
-    if (i >= kFxSlots && !(kFxTpSerialTail && comp && verb))
-      AD_HIP(hipStreamWaitEvent(s, h->ev[EA][k], 0));  // slot k consumed
+    FxStageArgs a = fx_chunk_args(h, d_buf, stride, n, T, i);
+    a.vT = eq ? a.vT : a.xT;  // the EQ output (or the input)
+    a.inT = nullptr;          // the staged engine's rows: not this engine's
+    a.coT = nullptr;
+    if (i >= kFxSlots) AD_HIP(hipStreamWaitEvent(s, h->ev[EA][k], 0));  // slot k consumed
     if (eq || comp) launch_fx_transpose_in(a, a.xT, s);  // the rows the EQ / the detector read
     if (eq) {
       FxTpEqArgs e{};
@@ -886,44 +813,17 @@ void fx_run_tp(ad_fx_chain* h, double* d_buf, int64_t stride, int64_t n, hipStre
       launch_fxtp_eq(e, true, s);
     }
     AD_HIP(hipEventRecord(h->ev[EE][k], s));
-    if (kFxTpSerialTail && comp && verb) {
-      // chunk i's detector on sd; chunk i - 1's gain and Freeverb on the
-      // caller's stream behind chunk i's EQ, so the chip-wide kernels never
-      // share CUs with K_verb (only the 32 detector CUs run beside both)
-      AD_HIP(hipStreamWaitEvent(sd, h->ev[EE][k], 0));
-      launch_fxtp_det(a, sd);
-      AD_HIP(hipEventRecord(h->ev[ED][k], sd));
-      if (i > 0) tail(prev, (int)((i - 1) % kFxSlots));
-      prev = a;
-      continue;
-    }
-    if (gain_on_s) {
-      AD_HIP(hipStreamWaitEvent(sd, h->ev[EE][k], 0));
-      launch_fxtp_det(a, sd);
-      AD_HIP(hipEventRecord(h->ev[ED][k], sd));
-      if (i > 0) gain_verb(prev, (int)((i - 1) % kFxSlots));
-      prev = a;
-      continue;
-    }
     if (comp) {
       AD_HIP(hipStreamWaitEvent(sd, h->ev[EE][k], 0));
       launch_fxtp_det(a, sd);
-      if (verb) {
-        // the compressor output channel-major into inC on the detector's
-        // stream (the reverb's stream is the longer one), then Freeverb into
-        // the user buffer; inC[k] is free once chunk i - kFxSlots's reverb ran
-        if (i >= kFxSlots) AD_HIP(hipStreamWaitEvent(sd, h->ev[EA][k], 0));
-        FxStageArgs b = a;
-        b.buf = h->inC[k].p;
-        b.stride = h->tmax;
-        launch_fx_gain(b, true, sd);
-      }
       AD_HIP(hipEventRecord(h->ev[ED][k], sd));
+      if (verb) {
+        if (i > 0) gain_verb(prev, (int)((i - 1) % kFxSlots));
+        prev = a;
+        continue;
+      }
       AD_HIP(hipStreamWaitEvent(sv, h->ev[ED][k], 0));
-      if (verb)
-        launch_fxtp_verb(a, h->inC[k].p, h->tmax, h->vbufC.p, h->coC.p, wu, sv);
-      else
-        launch_fx_gain(a, true, sv);
+      launch_fx_gain(a, true, sv);
     } else {  // no compressor (AD_FX_ENGINE_TIME_PARALLEL): the EQ output back, then Freeverb in place
       AD_HIP(hipStreamWaitEvent(sv, h->ev[EE][k], 0));
       if (eq) launch_fx_transpose_out(a, a.vT, sv);
@@ -931,12 +831,7 @@ void fx_run_tp(ad_fx_chain* h, double* d_buf, int64_t stride, int64_t n, hipStre
     }
     AD_HIP(hipEventRecord(h->ev[EA][k], sv));
   }
-  if (kFxTpSerialTail && comp && verb) {
-    tail(prev, k);  // the last chunk's gain and Freeverb, on s after its detector
-    AD_HIP(hipGetLastError());
-    return;
-  }
-  if (gain_on_s) gain_verb(prev, k);  // the last chunk's
+  if (comp && verb) gain_verb(prev, k);  // the last chunk's
   AD_HIP(hipGetLastError());
   AD_HIP(hipStreamWaitEvent(s, h->ev[EA][k], 0));  // the last chunk's reverb / output follows all work
 }
@@ -961,9 +856,9 @@ void fx_run(ad_fx_chain* h, double* d_buf, int64_t stride, int64_t n, hipStream_
       fx_run_tp(h, d_buf, stride, n, s);
       h->last_engine = AD_FX_ENGINE_TIME_PARALLEL;
     } else {
-      fx_run_staged(h, d_buf, stride, n, s);
-      h->last_engine =
-          (fx_eq_lanes(h) || fx_eq_split(h) || fx_eq_per_section(h)) ? AD_FX_ENGINE_STAGED : AD_FX_ENGINE_STAGED_NOSPLIT;
+      const FxPlan plan = fx_staged_plan(h);
+      fx_run_staged(h, plan, d_buf, stride, n, s);
+      h->last_engine = plan == FxPlan::WholeChain ? AD_FX_ENGINE_STAGED_NOSPLIT : AD_FX_ENGINE_STAGED;
     }
     AD_HIP(hipEventRecord(h->ev_last, s));
     return;
@@ -1119,12 +1014,6 @@ int ad_fx_chain_set_expander(ad_fx_chain* h, const ad_compressor_config* cfg, in
     if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "nil expander config");
     ad_compressor_config g = *cfg;
     check_comp_config(g);
-    if (!(g.ratio >= 1.0 && g.ratio <= 100.0)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "dynamics: ratio must be in [1, 100]");
-    if (!(g.knee_db >= 0.0 && g.knee_db <= 24.0)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "dynamics: knee must be in [0, 24] dB");
-    if (!(g.attack_ms >= 0.1 && g.attack_ms <= 1000.0))
-      AD_FAIL(AD_ERR_INVALID_ARGUMENT, "dynamics: attack must be in [0.1, 1000] ms");
-    if (!(g.release_ms >= 1.0 && g.release_ms <= 5000.0))
-      AD_FAIL(AD_ERR_INVALID_ARGUMENT, "dynamics: release must be in [1, 5000] ms");
     if (!(range_db >= -120.0 && range_db <= 0.0)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "dynamics: range must be in [-120, 0] dB");
     if (gate && !(hold_ms >= 0.0 && hold_ms <= 5000.0))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "dynamics: hold must be in [0, 5000] ms");
@@ -1316,19 +1205,14 @@ struct ad_fir {
   int device = 0, channels = 0;
   int64_t N = 0;
   hipStream_t stream = nullptr;       // host-buffer calls
-  hipStream_t last = nullptr;         // stream of the last call (valid when has_last)
-  bool has_last = false;              // a call has been enqueued (last may be the NULL stream)
-  hipEvent_t done = nullptr;          // recorded on `last` after each call's last operation
+  StreamOrder order;                  // calls may come on any stream
   DevBuf<double> h;                   // [N]
   DevBuf<double> hist[2];             // [C][N-1] delay line, ping-pong (cur = hist[cur])
   int cur = 0;
   DevBuf<double> stage;               // [C][n]: in-place calls read a copy of the input
   DevBuf<double> io_in, io_out;       // host-buffer calls
   ~ad_fir() {
-    if (done) {
-      (void)hipEventSynchronize(done);
-      (void)hipEventDestroy(done);
-    }
+    order.release();
     if (stream) {
       (void)hipStreamSynchronize(stream);
       (void)lib_stream_destroy(stream);
@@ -1348,7 +1232,7 @@ void fir_run(ad_fir* f, const double* d_src, int64_t src_stride, double* d_dst, 
   // The delay line, the staging copy and the ping-pong index are shared by
   // every stream a caller uses: a call on a new stream first waits for the
   // previous call's last operation.
-  if (f->has_last && f->last != s) AD_HIP(hipStreamWaitEvent(s, f->done, 0));
+  f->order.enter(s);
   const int64_t hn = f->N - 1;
   const size_t C = (size_t)f->channels;
   const char* s0 = reinterpret_cast<const char*>(d_src);
@@ -1363,18 +1247,7 @@ void fir_run(ad_fir* f, const double* d_src, int64_t src_stride, double* d_dst, 
     src_stride = n;
   }
   const double* hold = f->hist[f->cur].p;
-  if (hn > 0) {
-    double* hnew = f->hist[f->cur ^ 1].p;
-    if (n >= hn) {
-      AD_HIP(hipMemcpy2DAsync(hnew, hn * sizeof(double), d_src + (n - hn), src_stride * sizeof(double),
-                              hn * sizeof(double), C, hipMemcpyDeviceToDevice, s));
-    } else {
-      AD_HIP(hipMemcpy2DAsync(hnew, hn * sizeof(double), hold + n, hn * sizeof(double), (hn - n) * sizeof(double),
-                              C, hipMemcpyDeviceToDevice, s));
-      AD_HIP(hipMemcpy2DAsync(hnew + (hn - n), hn * sizeof(double), d_src, src_stride * sizeof(double),
-                              n * sizeof(double), C, hipMemcpyDeviceToDevice, s));
-    }
-  }
+  delay_line_next(f->hist[f->cur ^ 1].p, hold, hn, d_src, src_stride, n, C, s);
   FirArgs a{};
   a.h = f->h.p;
   a.N = f->N;
@@ -1389,9 +1262,7 @@ void fir_run(ad_fir* f, const double* d_src, int64_t src_stride, double* d_dst, 
   launch_fir(a, s);
   AD_HIP(hipGetLastError());
   if (hn > 0) f->cur ^= 1;
-  AD_HIP(hipEventRecord(f->done, s));
-  f->last = s;
-  f->has_last = true;
+  f->order.leave(s);
 }
 
 }  // namespace
@@ -1411,7 +1282,6 @@ int ad_fir_create(const double* coeffs, int64_t n_taps, int channels, int device
     f->channels = channels;
     f->N = n_taps;
     AD_HIP(lib_stream_create(&f->stream));
-    AD_HIP(hipEventCreateWithFlags(&f->done, hipEventDisableTiming));
     if (n_taps > 0) {
       f->h.alloc((size_t)n_taps);
       AD_HIP(hipMemcpy(f->h.p, coeffs, n_taps * sizeof(double), hipMemcpyHostToDevice));
@@ -1464,13 +1334,10 @@ int ad_fir_reset(ad_fir* f) {
   return guard([&] {
     if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null FIR handle");
     DeviceScope ds(f->device);
-    // after the last call, whatever stream (NULL included) it was enqueued on
-    if (f->has_last) AD_HIP(hipStreamWaitEvent(f->stream, f->done, 0));
+    f->order.join(f->stream);
     for (auto& hb : f->hist)
       if (hb.p) AD_HIP(hipMemsetAsync(hb.p, 0, hb.n * sizeof(double), f->stream));
-    AD_HIP(hipEventRecord(f->done, f->stream));
-    f->last = f->stream;
-    f->has_last = true;
+    f->order.leave(f->stream);
     AD_HIP(hipStreamSynchronize(f->stream));
   });
 }

@@ -10,6 +10,7 @@
 #include <utility>
 
 #include "ad_common.hpp"
+#include "stream_order.hpp"
 #include "fdn_kernels.hpp"
 
 using namespace adsp;
@@ -99,15 +100,10 @@ struct ad_fdn {
   DevBuf<double> phase;                 // [2]: lfoPhase, ping-pong (cur = phase[ph_cur])
   int ph_cur = 0;
   hipStream_t stream = nullptr;  // host-buffer calls, resets
-  hipStream_t last = nullptr;    // stream of the last call (valid when has_last)
-  bool has_last = false;
-  hipEvent_t done = nullptr;     // recorded on `last` after each call's last operation
+  StreamOrder order;             // calls may come on any stream
   DevBuf<double> io;             // host-buffer calls
   ~ad_fdn() {
-    if (done) {
-      (void)hipEventSynchronize(done);
-      (void)hipEventDestroy(done);
-    }
+    order.release();
     if (stream) {
       (void)hipStreamSynchronize(stream);
       (void)lib_stream_destroy(stream);
@@ -124,10 +120,6 @@ void update_gains(ad_fdn* f) {  // updateFeedbackGains :303-312
   }
 }
 
-void wait_last(ad_fdn* f) {
-  if (f->has_last) AD_HIP(hipEventSynchronize(f->done));
-}
-
 void zero(ad_fdn* f, DevBuf<double>& b) {
   if (b.p) AD_HIP(hipMemsetAsync(b.p, 0, b.n * sizeof(double), f->stream));
 }
@@ -137,7 +129,7 @@ void zero(ad_fdn* f, DevBuf<double>& b) {
 // their contents; every filterState is zeroed; the gains are recomputed.  The
 // new lines are allocated before anything is replaced.
 void reconfigure(ad_fdn* f, const Derived& nd) {
-  wait_last(f);
+  f->order.wait_host();
   const size_t C = (size_t)f->channels;
   DevBuf<double> fresh[kFdnLines + 1];
   for (int i = 0; i <= kFdnLines; ++i) {
@@ -164,7 +156,7 @@ int block_of(const ad_fdn* f) {  // max(1, P): consecutive samples whose reads s
 int sub_of(const ad_fdn* f) { return std::min(block_of(f), kFdnMaxSub); }
 
 void fdn_run(ad_fdn* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
-  if (f->has_last && f->last != s) AD_HIP(hipStreamWaitEvent(s, f->done, 0));
+  f->order.enter(s);
   FdnArgs a{};
   a.buf = d_buf;
   a.stride = stride;
@@ -198,9 +190,7 @@ void fdn_run(ad_fdn* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s)
   for (int i = 0; i < kFdnLines; ++i) f->wp[i] = (int)((f->wp[i] + n) % f->d.len[i]);
   if (f->d.pre_delay > 0) f->pre_wp = (int)((f->pre_wp + n) % f->d.pre_len);  // written only then (:202-205)
   f->ph_cur ^= 1;
-  AD_HIP(hipEventRecord(f->done, s));
-  f->last = s;
-  f->has_last = true;
+  f->order.leave(s);
 }
 
 }  // namespace
@@ -242,7 +232,6 @@ int ad_fdn_create(const ad_fdn_config* cfg, int channels, int device, ad_fdn** o
     f->channels = channels;
     f->cfg = *cfg;
     AD_HIP(lib_stream_create(&f->stream));
-    AD_HIP(hipEventCreateWithFlags(&f->done, hipEventDisableTiming));
     f->fstate.alloc((size_t)channels * kFdnLines);
     f->phase.alloc(2);
     AD_HIP(hipMemsetAsync(f->phase.p, 0, 2 * sizeof(double), f->stream));
@@ -308,7 +297,7 @@ int ad_fdn_derived(const ad_fdn* f, double feedback_gain[8], int64_t line_len[8]
     if (pre_len) *pre_len = f->d.pre_len;
     if (lfo_phase) {
       DeviceScope ds(f->device);
-      if (f->has_last) AD_HIP(hipEventSynchronize(f->done));
+      f->order.wait_host();
       AD_HIP(hipMemcpy(lfo_phase, f->phase.p + f->ph_cur, sizeof(double), hipMemcpyDeviceToHost));
     }
   });
@@ -353,7 +342,7 @@ int ad_fdn_reset(ad_fdn* f) {
   return guard([&] {
     if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null fdn reverb handle");
     DeviceScope ds(f->device);
-    wait_last(f);
+    f->order.wait_host();
     for (auto& l : f->line) zero(f, l);
     zero(f, f->pre);
     zero(f, f->fstate);

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "ad_common.hpp"
+#include "stream_order.hpp"
 #include "resample_kernels.hpp"
 
 using namespace adsp;
@@ -39,18 +40,13 @@ struct ad_resampler {
   int64_t phase = 0, ahead = 0;
   ResamplePlan plan;
   hipStream_t stream = nullptr;  // host-buffer calls
-  hipStream_t last = nullptr;    // stream of the last call (valid when has_last)
-  bool has_last = false;
-  hipEvent_t done = nullptr;     // recorded on `last` after each call's last operation
+  StreamOrder order;             // calls may come on any stream
   DevBuf<double> tab;            // [up][pitch], phase-major
   DevBuf<double> hist[2];        // [C][T-1] delay line, ping-pong (cur = hist[cur])
   int cur = 0;
   DevBuf<double> io_in, io_out;  // host-buffer calls
   ~ad_resampler() {
-    if (done) {
-      (void)hipEventSynchronize(done);
-      (void)hipEventDestroy(done);
-    }
+    order.release();
     if (stream) {
       (void)hipStreamSynchronize(stream);
       (void)lib_stream_destroy(stream);
@@ -83,22 +79,11 @@ void check_n_out(int64_t n_out) {
 // is built in the other history buffer, so nothing the kernel reads is written.
 void resample_run(ad_resampler* r, const double* d_in, int64_t in_stride, int64_t n_in, double* d_out,
                   int64_t out_stride, int64_t n_out, hipStream_t s) {
-  if (r->has_last && r->last != s) AD_HIP(hipStreamWaitEvent(s, r->done, 0));
+  r->order.enter(s);
   const int64_t hn = r->T - 1;
   const size_t C = (size_t)r->channels;
   const double* hold = r->hist[r->cur].p;
-  if (hn > 0) {
-    double* hnew = r->hist[r->cur ^ 1].p;
-    if (n_in >= hn) {
-      AD_HIP(hipMemcpy2DAsync(hnew, hn * sizeof(double), d_in + (n_in - hn), in_stride * sizeof(double),
-                              hn * sizeof(double), C, hipMemcpyDeviceToDevice, s));
-    } else {
-      AD_HIP(hipMemcpy2DAsync(hnew, hn * sizeof(double), hold + n_in, hn * sizeof(double),
-                              (hn - n_in) * sizeof(double), C, hipMemcpyDeviceToDevice, s));
-      AD_HIP(hipMemcpy2DAsync(hnew + (hn - n_in), hn * sizeof(double), d_in, in_stride * sizeof(double),
-                              n_in * sizeof(double), C, hipMemcpyDeviceToDevice, s));
-    }
-  }
+  delay_line_next(r->hist[r->cur ^ 1].p, hold, hn, d_in, in_stride, n_in, C, s);
   if (n_out > 0) {
     ResampleArgs a{};
     a.tab = r->tab.p;
@@ -123,9 +108,7 @@ void resample_run(ad_resampler* r, const double* d_in, int64_t in_stride, int64_
   const int64_t num = r->phase + n_out * r->down;
   r->ahead += num / r->up - n_in;
   r->phase = num % r->up;
-  AD_HIP(hipEventRecord(r->done, s));
-  r->last = s;
-  r->has_last = true;
+  r->order.leave(s);
 }
 
 }  // namespace
@@ -166,7 +149,6 @@ int ad_resampler_create(int64_t up, int64_t down, const double* taps, int64_t n_
     r->T = T;
     r->plan = resample_plan(up, down, T);
     AD_HIP(lib_stream_create(&r->stream));
-    AD_HIP(hipEventCreateWithFlags(&r->done, hipEventDisableTiming));
     r->tab.alloc(tab.size());
     AD_HIP(hipMemcpy(r->tab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     if (T > 1) {
@@ -243,12 +225,10 @@ int ad_resampler_reset(ad_resampler* r) {
   return guard([&] {
     if (!r) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null resampler handle");
     DeviceScope ds(r->device);
-    if (r->has_last) AD_HIP(hipStreamWaitEvent(r->stream, r->done, 0));
+    r->order.join(r->stream);
     for (auto& hb : r->hist)
       if (hb.p) AD_HIP(hipMemsetAsync(hb.p, 0, hb.n * sizeof(double), r->stream));
-    AD_HIP(hipEventRecord(r->done, r->stream));
-    r->last = r->stream;
-    r->has_last = true;
+    r->order.leave(r->stream);
     AD_HIP(hipStreamSynchronize(r->stream));
     r->phase = 0;
     r->ahead = 0;

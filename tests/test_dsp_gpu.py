@@ -762,12 +762,14 @@ def test_convolution_reverb(gpu, min_order):
     assert rms(got, want) <= 1e-7
 
 
-def test_eq_only_per_section_pipeline_bit_exact(gpu):
-    """EQ-only chains (a12-a14) run one K_sec workgroup per section, each on
-    its own chunk (fx_run_staged): bit-exact against the oracle's
-    biquad.Chain.ProcessBlock (chain.go:59-70, section.go:47-53) over several
-    16384-sample chunks, calls that end mid-step and mid-chunk, a partial
-    channel group (130 channels), and the EQ state afterwards."""
+def test_eq_only_lanes_several_calls_bit_exact(gpu):
+    """An EQ-only chain (a12-a14) at 130 channels runs K_lanes (one launch per
+    call, in place on the buffer): bit-exact against the oracle's
+    biquad.Chain.ProcessBlock (chain.go:59-70, section.go:47-53) over three
+    calls of 17001, 39 and 22960 samples, the EQ state carried from call to
+    call, on the first and last channels of both 64-channel groups (the
+    second one partial).  The per-section pipeline, which EQ-only chains ran
+    before K_lanes, is pinned by test_staged_engine_matches_fused[eq-verb]."""
     fs = 48000.0
     eq = design.config5_eq(fs)
     C, n = 130, 40000

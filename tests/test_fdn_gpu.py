@@ -152,6 +152,35 @@ def test_results_do_not_depend_on_call_boundaries(gpu):
     assert h3.derived()[3] == h.derived()[3]
 
 
+def test_mixed_streams(gpu):
+    """Calls on the NULL stream, a side stream and the host-buffer path, then
+    Reset while a side-stream call is the last one enqueued, then the same
+    again: the lines are shared by every stream, each call waits for the
+    previous call's last operation, so the result is one sequential reverb's.
+    44.1 kHz: the longest line (3067) is longer than every call, so the
+    feedback crosses each call boundary.  Mod depth 0: bit-exact."""
+    C, n = 3, 4000
+    h, refs = pair(44100.0, C, [("SetModDepth", 0.0)])
+    x = noise(n, C)
+    want = [r.process(x[c]) for c, r in enumerate(refs)]
+    d = torch.empty((C, n), dtype=torch.float64, device=DEV)
+    side = torch.cuda.Stream()
+    for rep in range(2):
+        d.copy_(torch.from_numpy(x))
+        h.process_device(d.data_ptr(), n, 1000, 0)
+        h.process_device(d.data_ptr() + 8 * 1000, n, 1000, side.cuda_stream)
+        blk = x[:, 2000:2500].copy()
+        h.ProcessInPlace(blk)
+        h.process_device(d.data_ptr() + 8 * 2500, n, 1500, 0)
+        torch.cuda.synchronize()
+        got = d.cpu().numpy()
+        got[:, 2000:2500] = blk
+        for c in range(C):
+            compare(got[c], want[c], True, f"round {rep} channel {c}")
+        h.process_device(d.data_ptr(), n, 700, side.cuda_stream)
+        h.Reset()
+
+
 # ---- 5. many channels -------------------------------------------------------
 def test_seventy_channels(gpu):
     C, n, silent = 70, 1024, 33

@@ -174,6 +174,44 @@ def test_streaming_one_sample_calls(gpu, up, down, T):
     assert y.shape[1] == len(one.process_vec(x[0]))
 
 
+def test_mixed_streams(gpu):
+    """Calls on the NULL stream, a side stream and the host-buffer path, then
+    Reset while a side-stream call is the last one enqueued, then the same
+    again: the delay line and the phase are shared by every stream, each call
+    waits for the previous call's last operation, so the outputs are one
+    sequential resampler's.  5/3 with 64 taps per phase: the 40-sample call is
+    shorter than the delay line (63), which is then built from its own tail
+    and the input."""
+    import torch
+
+    up, down, T, n = 5, 3, 64, 1500
+    x = signal(n)[:2].copy()
+    w = want(up, down, T, "random", n)[0][:2]  # channels are independent
+    cap = w.shape[1]
+    r = make(up, down, T, "random", channels=2)
+    dx = torch.from_numpy(x).cuda()
+    spare = torch.empty((2, 200), dtype=torch.float64, device=DEV)
+    side = torch.cuda.Stream()
+    for rep in range(2):
+        dy = torch.full((2, cap), float("nan"), dtype=torch.float64, device=DEV)
+        sync()
+        pos = out = 0
+        for m, where in [(600, 0), (40, side.cuda_stream), (360, "host"), (500, 0)]:
+            if where == "host":
+                host_at, host_y = out, r.Process(np.ascontiguousarray(x[:, pos:pos + m]))
+                no = host_y.shape[1]
+            else:
+                no = r.process_device(dx.data_ptr() + 8 * pos, n, m, dy.data_ptr() + 8 * out, cap, cap - out, where)
+            pos, out = pos + m, out + no
+        sync()
+        got = dy.cpu().numpy()
+        got[:, host_at:host_at + host_y.shape[1]] = host_y
+        assert out == cap and same(got, w), rep
+        r.process_device(dx.data_ptr(), n, 100, spare.data_ptr(), 200, 200, side.cuda_stream)
+        r.Reset()
+    r.close()
+
+
 def test_zero_output_calls_write_nothing(gpu):
     """1/6 fed 3 samples at a time: the calls that yield no output return
     success, leave a NaN-filled output untouched (host and device form), and

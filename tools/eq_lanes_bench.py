@@ -1,11 +1,8 @@
 """EQ-only chains (a12-a14, bit-exact): K_lanes (the default, AUTO) against the
-staged one-workgroup kernel (ENGINE_STAGED_NOSPLIT) and, up to 4096 channels,
-the per-section pipeline (an AD_FX_EQ_LANES=0 build, when given as argv[1]):
-ms per call and Gsamples/s at config 5's five sections, several channel
-counts, device-resident buffers, the same input for every engine (outputs
-compared bit for bit)."""
-import ctypes as C
-import os
+staged one-workgroup kernel (ENGINE_STAGED_NOSPLIT): ms per call and
+Gsamples/s at config 5's five sections, several channel counts,
+device-resident buffers, the same input for every engine (outputs compared
+bit for bit)."""
 import pathlib
 import sys
 import time
