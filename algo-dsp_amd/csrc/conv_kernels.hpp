@@ -89,7 +89,6 @@ struct RfftArgs {
   int64_t s0;           // first sample of chunk block 0 (call-relative)
   int jc;               // blocks per channel in this launch
   int channels;
-  int aligned;          // x and x_stride allow 16-byte pair loads
   double2* X;           // block-spectra ring [C][Q][MS]
   int64_t x_ch_stride;  // Q*MS
   int Q;
@@ -161,7 +160,6 @@ struct IrfftArgs {
   int64_t o0;           // output sample of chunk block 0
   int jc;
   int channels;
-  int aligned;
   int accumulate;       // 1: add into out (partitioned stages sharing one accumulator)
   const double2* twM;
   const double2* twN;

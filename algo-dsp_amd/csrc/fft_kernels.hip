@@ -30,21 +30,133 @@
 
 namespace adsp {
 
+// A row of doubles starts on a 16-byte boundary or exactly 8 bytes past one.
+// Every kernel here decides that per item from the row's own base (wave- or
+// transform-uniform), so a [C][odd stride] buffer keeps 16-byte accesses on
+// all of its rows: the even rows as they are, the odd ones shifted by one
+// double (below).
+__device__ __forceinline__ bool off16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 8) != 0; }
+
+// Lane l takes lane l + 1's value (lane 63 keeps its own): a DPP wavefront
+// shift per dword, VALU only.
+__device__ __forceinline__ double lane_up(double v) {
+  constexpr int kWaveShl1 = 0x130;
+  const int lo = __double2loint(v), hi = __double2hiint(v);
+  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, kWaveShl1, 0xf, 0xf, false),
+                          __builtin_amdgcn_update_dpp(lo, lo, kWaveShl1, 0xf, 0xf, false));
+}
+
+// The value itself, as a move the compiler keeps (an identity quad
+// permutation).  store_pair_shifted's 16-byte operand is (v.y, neighbour's
+// v.x); built from v.y directly, the register coalescer made v.y the low half
+// of that four-VGPR operand for its whole life, two idle VGPRs per slot
+// beside every accumulator of k_irfft_mix_split's channel loop (226 -> 256
+// VGPRs and 36 B/lane of scratch at M = 8192, V = 16).
+__device__ __forceinline__ double lane_copy(double v) {
+  constexpr int kQuadIdentity = 0xE4;
+  const int lo = __double2loint(v), hi = __double2hiint(v);
+  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, kQuadIdentity, 0xf, 0xf, false),
+                          __builtin_amdgcn_update_dpp(lo, lo, kQuadIdentity, 0xf, 0xf, false));
+}
+
+// The transforms below leave (and take) their values with consecutive lanes
+// on consecutive indices: slot s of lane tid is index tid + s T, on the way
+// in (pass 0, per butterfly) and on the way out (the last pass is one radix-V
+// butterfly per lane with stride T).  The shifted paths rest on that.
+template <int M, int V>
+struct LaneOrder {
+  using Plan = FftPlan<M, V>;
+  static_assert(Plan::radix(Plan::NPASS - 1) == V && Plan::ns(Plan::NPASS - 1) == Plan::T,
+                "last_pass_index(tid, s) == tid + s T: consecutive lanes hold consecutive outputs");
+  static_assert(Plan::R0 >= 2 && (V / Plan::R0) * Plan::T == M / Plan::R0,
+                "pass0_index(tid, s) == tid + b T + r M/R0: consecutive lanes hold consecutive inputs");
+  // lanes of one wave that hold one run of consecutive indices
+  static constexpr int G = Plan::T < 64 ? Plan::T : 64;
+  static_assert(G == 64 || Plan::T == G, "a transform's lanes are whole waves or one part of a wave");
+};
+
+// One slot of a full block on a row 8 bytes off alignment.  Lane gl of a
+// group of G consecutive lanes holds v = (y[2m], y[2m+1]), p = &y[2m],
+// consecutive lanes consecutive m.  p + 1 is 16-byte aligned and takes
+// (y[2m+1], y[2m+2]), y[2m+2] being lane gl + 1's v.x (one in-wave exchange);
+// the group's two edge values, lane 0's v.x and lane G-1's v.y, go out as
+// 8-byte singles in one more instruction.  Nothing outside the group's own
+// 2G doubles is touched: the neighbours belong to other waves or workgroups.
+// The values stored are the registers the aligned path stores.  NT applies
+// to the 16-byte stores.
+template <int G, bool NT, bool ACC>
+__device__ __forceinline__ void store_pair_shifted(double* p, double2 v, int gl) {
+  static_assert(G >= 2, "lane 0 and lane G-1 are different lanes");
+  const double nx = lane_up(v.x);
+  if (gl < G - 1) {
+    double2* q = reinterpret_cast<double2*>(p + 1);
+    double2 r = make_double2(lane_copy(v.y), nx);
+    if constexpr (ACC) {
+      const double2 o = *q;
+      r = make_double2(o.x + r.x, o.y + r.y);
+    }
+    st2<NT>(q, r);
+  }
+  if (gl == 0 || gl == G - 1) {
+    double* e = p + (gl == 0 ? 0 : 1);  // a 32-bit select: the row base stays scalar
+    double r = gl == 0 ? v.x : v.y;
+    if constexpr (ACC) r = *e + r;
+    // default cache policy also under NT: the single shares its 32-byte sector
+    // with the neighbouring wave's single and this wave's first 16-byte
+    // store, and written non-temporally the three reached HBM apart (K3's
+    // WRITE_SIZE 277.1 MB against 270.5 algorithmic; 272.1 this way)
+    *e = r;
+  }
+}
+
+// The load counterpart: the lane wants (x[t], x[t+1]), p = &x[t] 8 bytes off,
+// consecutive lanes consecutive pairs.  Lanes 1.. load the aligned slot
+// (x[t-1], x[t]) and take x[t+1] from lane gl + 1's slot; lane 0's x[t] and
+// lane G-1's x[t+1] are singles (the slot below lane 0 may lie outside the
+// buffer).
+template <int G>
+__device__ __forceinline__ double2 load_pair_shifted(const double* p, int gl) {
+  static_assert(G >= 2, "lane 0 and lane G-1 are different lanes");
+  double2 q = make_double2(0.0, 0.0);
+  if (gl > 0) q = *reinterpret_cast<const double2*>(p - 1);
+  double e = 0.0;
+  if (gl == 0 || gl == G - 1) e = p[gl == 0 ? 0 : 1];
+  const double nx = lane_up(q.x);
+  return make_double2(gl == 0 ? e : q.y, gl == G - 1 ? e : nx);
+}
+
 __device__ __forceinline__ double2 fetch_pair(const double* xc, int64_t t, int64_t n, bool aligned) {
   if (t + 1 < n && aligned) return *reinterpret_cast<const double2*>(xc + t);
   return make_double2(t < n ? xc[t] : 0.0, t + 1 < n ? xc[t + 1] : 0.0);
 }
 
-// Inverse store: the upper half of the time window (m >= M/2) to y.
+// Inverse store: the upper half of the time window (m >= M/2, slots s >= V/2)
+// to y.  The row's alignment and whether the block is whole are uniform over
+// the transform's lanes.
 template <int M, int V>
 __device__ __forceinline__ void irfft_store_out(const double2* v, int tid, double* yc, int64_t ob, int64_t out_len,
-                                                bool aligned, bool acc) {
+                                                bool acc) {
+  constexpr int G = LaneOrder<M, V>::G;
+  const bool off = off16(yc + ob);  // ob + 2m has ob's parity
+  if constexpr (G >= 2) {
+    if (off && ob + 2 * M <= out_len) {
+#pragma unroll
+      for (int s = V / 2; s < V; ++s) {
+        double* p = yc + ob + 2 * last_pass_index<M, V>(tid, s);
+        if (acc)
+          store_pair_shifted<G, false, true>(p, v[s], tid);
+        else
+          store_pair_shifted<G, false, false>(p, v[s], tid);
+      }
+      return;
+    }
+  }
 #pragma unroll
   for (int s = 0; s < V; ++s) {
     const int m = last_pass_index<M, V>(tid, s);
     if (m < M / 2) continue;
     const int64_t o = ob + 2 * m;
-    if (o + 1 < out_len && aligned) {
+    if (o + 1 < out_len && !off) {
       double2 r = v[s];
       if (acc) {
         const double2 q = *reinterpret_cast<const double2*>(yc + o);
@@ -119,11 +231,22 @@ __global__ __launch_bounds__((FftPlan<M, V>::BLOCK)) void k_window_rfft(RfftArgs
   const double* xc = a.x + (int64_t)c * a.x_stride;
   const int64_t t0 = a.s0 + (int64_t)j * L;  // first sample of block j
 
+  // m < M/2 (the rest is the block's zero padding) is r < R0/2 of the slot
+  constexpr int R0 = Plan::R0, G = LaneOrder<M, V>::G;
+  const bool off = off16(xc + t0);
+  const bool shifted = G >= 2 && active && off && t0 + L <= a.n;  // uniform over the transform's lanes
   double2 v[V];
 #pragma unroll
   for (int s = 0; s < V; ++s) {
     const int m = pass0_index<M, V>(tid, s);
-    v[s] = (active && m < M / 2) ? fetch_pair(xc, t0 + 2 * m, a.n, a.aligned) : make_double2(0, 0);
+    const bool live = s % R0 < R0 / 2;
+    if constexpr (G >= 2) {
+      if (live && shifted) {
+        v[s] = load_pair_shifted<G>(xc + t0 + 2 * m, tid);
+        continue;
+      }
+    }
+    v[s] = (active && live) ? fetch_pair(xc, t0 + 2 * m, a.n, !off) : make_double2(0, 0);
   }
   fft_run<M, V, true>(v, tid, lds, TwGlobal{a.twM});
   if (!active) return;
@@ -154,7 +277,7 @@ __global__ __launch_bounds__((FftPlan<M, V>::BLOCK)) void k_irfft_store(IrfftArg
   }
   fft_run<M, V, false>(v, tid, lds, TwGlobal{a.twM});
   if (!active) return;
-  irfft_store_out<M, V>(v, tid, a.out + (int64_t)c * a.out_stride, a.o0 + (int64_t)j * L - M, a.out_len, a.aligned,
+  irfft_store_out<M, V>(v, tid, a.out + (int64_t)c * a.out_stride, a.o0 + (int64_t)j * L - M, a.out_len,
                         a.accumulate);
 }
 
@@ -293,7 +416,32 @@ __global__ __launch_bounds__((SplitPlan<M, VV>::T)) __attribute__((amdgpu_waves_
   // s mod R0 >= R0/2 (pass0_index >= M2/2), known at compile time.
   constexpr int R0 = FftPlan<M2, V>::R0;
   double2 ev[V], ov[V];
-  if (a.aligned && t0 + L <= a.n) {  // wave-uniform fast path
+  const bool off = off16(xc + t0);  // this item's row: wave-uniform
+  if (off && t0 + L <= a.n) {
+    // the row is 8 bytes off: the aligned slots are (x[4p-1], x[4p]) and
+    // (x[4p+1], x[4p+2]); x[4p+3] is the next lane's first slot.  The wave's
+    // first x[4p] and last x[4p+3] are singles.
+    constexpr int G = LaneOrder<M2, V>::G;
+    static_assert(G == 64, "whole waves");
+    const int gl = tid & 63;
+#pragma unroll
+    for (int s = 0; s < V; ++s) {
+      if (s % R0 < R0 / 2) {
+        const double* p = xc + t0 + 4 * pass0_index<M2, V>(tid, s);
+        double2 q0 = make_double2(0.0, 0.0);
+        if (gl > 0) q0 = *reinterpret_cast<const double2*>(p - 1);
+        const double2 q1 = *reinterpret_cast<const double2*>(p + 1);
+        double e = 0.0;
+        if (gl == 0 || gl == 63) e = p[gl == 0 ? 0 : 3];
+        const double nx = lane_up(q0.x);
+        ev[s] = make_double2(gl == 0 ? e : q0.y, q1.x);
+        ov[s] = make_double2(q1.y, gl == 63 ? e : nx);
+      } else {
+        ev[s] = make_double2(0.0, 0.0);
+        ov[s] = make_double2(0.0, 0.0);
+      }
+    }
+  } else if (!off && t0 + L <= a.n) {  // wave-uniform fast path
     // E's inputs first: its transform starts while O's are still in flight
 #pragma unroll
     for (int s = 0; s < V; ++s)
@@ -308,8 +456,8 @@ __global__ __launch_bounds__((SplitPlan<M, VV>::T)) __attribute__((amdgpu_waves_
     for (int s = 0; s < V; ++s) {
       const int64_t t = t0 + 4 * pass0_index<M2, V>(tid, s);
       const bool live = s % R0 < R0 / 2;
-      ev[s] = live ? fetch_pair(xc, t, a.n, a.aligned) : make_double2(0.0, 0.0);
-      ov[s] = live ? fetch_pair(xc, t + 2, a.n, a.aligned) : make_double2(0.0, 0.0);
+      ev[s] = live ? fetch_pair(xc, t, a.n, !off) : make_double2(0.0, 0.0);
+      ov[s] = live ? fetch_pair(xc, t + 2, a.n, !off) : make_double2(0.0, 0.0);
     }
   }
   const TwLds<M2> twS = tw_lds_compute<M2>(lds + FftPlan<M2, V>::MP, tid, T);
@@ -383,7 +531,21 @@ __global__ __launch_bounds__((SplitPlan<M, VV>::T)) __attribute__((amdgpu_waves_
     const int m = last_pass_index<M2, V>(tid, s);
     av[s] = c_sub(av[s], c_mul(c_conj(twC(m)), bv[s]));
   }
-  if (a.aligned && ob + 2 * M2 <= a.out_len) {  // wave-uniform fast paths
+  const bool off = off16(yb);  // this item's row: wave-uniform
+  if (off && ob + 2 * M2 <= a.out_len) {
+    // 8 bytes off: the same registers through the 16-byte slots one double up
+    constexpr int G = LaneOrder<M2, V>::G;
+    static_assert(G == 64, "whole waves");
+    if (!a.accumulate) {
+#pragma unroll
+      for (int s = 0; s < V; ++s)
+        store_pair_shifted<G, NT, false>(yb + 2 * last_pass_index<M2, V>(tid, s), av[s], tid & 63);
+    } else {
+#pragma unroll
+      for (int s = 0; s < V; ++s)
+        store_pair_shifted<G, false, true>(yb + 2 * last_pass_index<M2, V>(tid, s), av[s], tid & 63);
+    }
+  } else if (!off && ob + 2 * M2 <= a.out_len) {  // wave-uniform fast paths
     if (!a.accumulate) {
 #pragma unroll
       for (int s = 0; s < V; ++s)
@@ -480,7 +642,14 @@ __global__ __launch_bounds__((SplitPlan<M, VV>::T)) __attribute__((amdgpu_waves_
   }
   const int64_t ob = a.o0 + (int64_t)j * L;  // output of time index M/2 + m is at ob + 2m
   double* yb = a.out + (int64_t)side * a.out_stride + ob;
-  if (a.aligned && ob + 2 * M2 <= a.out_len) {
+  const bool off = off16(yb);  // this side's mix row
+  if (off && ob + 2 * M2 <= a.out_len) {
+    constexpr int G = LaneOrder<M2, V>::G;
+    static_assert(G == 64, "whole waves");
+#pragma unroll
+    for (int s = 0; s < V; ++s)
+      store_pair_shifted<G, NT, false>(yb + 2 * last_pass_index<M2, V>(tid, s), acc[s], tid & 63);
+  } else if (!off && ob + 2 * M2 <= a.out_len) {
 #pragma unroll
     for (int s = 0; s < V; ++s) st2<NT>(reinterpret_cast<double2*>(yb + 2 * last_pass_index<M2, V>(tid, s)), acc[s]);
   } else {

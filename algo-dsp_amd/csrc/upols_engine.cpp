@@ -71,7 +71,6 @@ Upols::Upols(int device, const double* kernels, int n_ir, int64_t K, int L, int 
   a.s0 = 0;
   a.jc = 1;
   a.channels = (int)nparts;
-  a.aligned = 1;
   a.X = H_.p;
   a.x_ch_stride = MS_;
   a.Q = 1;
@@ -250,7 +249,6 @@ void Upols::k1(const Chunk& ck, const Rings& rg, const Io& io, const StreamGate&
   a.s0 = ck.cs * L_;
   a.jc = ck.jin;
   a.channels = C_;
-  a.aligned = io.in_aligned;
   a.X = rg.X;
   a.x_ch_stride = (int64_t)(rg.Q + 1) * MS_;
   a.Q = rg.Q;
@@ -312,7 +310,6 @@ void Upols::k3(const Chunk& ck, const Rings& rg, const Io& io, const StreamGate&
   b.o0 = ck.cs * L_;
   b.jc = ck.jc;
   b.channels = C_;
-  b.aligned = io.out_aligned;
   b.accumulate = io.accumulate ? 1 : 0;
   b.twM = tw_.p;
   b.twN = tw_.p + M_;
@@ -378,15 +375,11 @@ void Upols::run(const double* d_in, int64_t in_stride, int64_t n, double* d_out,
   io.in = d_in;
   io.in_stride = in_stride;
   io.n = n;
-  io.in_aligned = ((reinterpret_cast<uintptr_t>(d_in) & 15) == 0) && (in_stride % 2 == 0);
   io.out = d_out;
   io.out_stride = out_stride;
   io.out_len = out_len;
   io.accumulate = accumulate;
   io.mix = mix;
-  const double* op = mix ? mix->p : d_out;
-  const int64_t ostr = mix ? mix->stride : out_stride;
-  io.out_aligned = ((reinterpret_cast<uintptr_t>(op) & 15) == 0) && (ostr % 2 == 0);
   // call blocks holding input samples: [0, nb_in); K1 transforms only those,
   // K2 reads every later block as zeros
   const int64_t nb_in = (std::max<int64_t>(n, 0) + L_ - 1) / L_;

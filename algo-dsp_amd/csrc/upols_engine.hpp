@@ -140,10 +140,8 @@ class Upols {
   struct Io {
     const double* in;
     int64_t in_stride, n;
-    int in_aligned;
     double* out;
     int64_t out_stride, out_len;
-    int out_aligned;
     bool accumulate;
     const MixOut* mix;
   };
