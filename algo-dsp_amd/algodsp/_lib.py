@@ -110,6 +110,20 @@ class FdnConfig(C.Structure):
                                           "mod_depth_seconds", "mod_rate_hz")]
 
 
+class DelayConfig(C.Structure):
+    """ad_delay_config (include/algodsp.h)."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "time_seconds", "feedback", "mix", "smooth_coeff")] + \
+               [("mode", C.c_int), ("delay_samples", C.c_int64)]
+
+
+class FlangerConfig(C.Structure):
+    """ad_flanger_config (include/algodsp.h); field k is parameter AD_FLANGER_* = k."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "rate_hz", "depth_seconds", "base_delay_seconds", "feedback",
+                                          "mix")]
+
+
 class DeconvOptionsC(C.Structure):
     """ad_deconv_options (include/algodsp.h)."""
 
@@ -271,6 +285,29 @@ def _declare(L: C.CDLL) -> None:
         "ad_fdn_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
         "ad_fdn_reset": (C.c_int, [vp]),
         "ad_fdn_destroy": (None, [vp]),
+        "ad_delay_default_config": (None, [C.POINTER(DelayConfig), C.c_double]),
+        "ad_delay_validate": (C.c_int, [C.POINTER(DelayConfig)]),
+        "ad_delay_create": (C.c_int, [C.POINTER(DelayConfig), C.c_int, C.c_int, C.POINTER(vp)]),
+        "ad_delay_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
+        "ad_delay_get_config": (C.c_int, [vp, C.POINTER(DelayConfig)]),
+        "ad_delay_derived": (C.c_int, [vp, c_double_p, c_double_p, c_int64_p, c_int64_p]),
+        "ad_delay_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 4),
+        "ad_delay_set_regime": (C.c_int, [vp, C.c_int]),
+        "ad_delay_process": (C.c_int, [vp, c_double_p, i64]),
+        "ad_delay_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
+        "ad_delay_reset": (C.c_int, [vp]),
+        "ad_delay_destroy": (None, [vp]),
+        "ad_flanger_default_config": (None, [C.POINTER(FlangerConfig), C.c_double]),
+        "ad_flanger_validate": (C.c_int, [C.POINTER(FlangerConfig)]),
+        "ad_flanger_create": (C.c_int, [C.POINTER(FlangerConfig), C.c_int, C.c_int, C.POINTER(vp)]),
+        "ad_flanger_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
+        "ad_flanger_get_config": (C.c_int, [vp, C.POINTER(FlangerConfig)]),
+        "ad_flanger_derived": (C.c_int, [vp, c_int64_p, c_int64_p, c_int64_p, c_double_p]),
+        "ad_flanger_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 4),
+        "ad_flanger_process": (C.c_int, [vp, c_double_p, i64]),
+        "ad_flanger_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
+        "ad_flanger_reset": (C.c_int, [vp]),
+        "ad_flanger_destroy": (None, [vp]),
         "ad_correlate_fft": (C.c_int, [c_double_p, i64, c_double_p, i64, c_double_p, C.c_int]),
         "ad_correlate_fft_device": (C.c_int, [vp, i64, vp, i64, vp, C.c_int, vp]),
         "ad_deconv_default_options": (DeconvOptionsC, []),

@@ -14,7 +14,8 @@ chain_process.go:177-227 for split-freq).  The compiled node list goes to
 ad_fx_graph_create (include/algodsp.h), which runs every node on the GPU;
 there is no CPU path.  Node types outside {filter*, dyn-compressor,
 dyn-limiter, dyn-gate, dyn-expander, reverb-freeverb, reverb-fdn, reverb,
-reverb-conv, split-freq, split, sum, _input, _output} raise
+reverb-conv, delay, delay-simple, flanger, split-freq, split, sum, _input,
+_output} raise
 UnknownEffect (the GPU runtime's ErrUnknownEffect).
 """
 from __future__ import annotations
@@ -26,7 +27,7 @@ import math
 import numpy as np
 
 from . import design
-from ._lib import CompressorConfig, FdnConfig, check, lib, ptr
+from ._lib import CompressorConfig, DelayConfig, FdnConfig, FlangerConfig, check, lib, ptr
 from .processors import section_table
 
 INPUT_NODE_ID = "_input"  # graph.go:10-13
@@ -35,6 +36,7 @@ NODE_TYPE_SPLIT_FREQ = "split-freq"
 
 FXN_INPUT, FXN_OUTPUT, FXN_PASS, FXN_SPLIT_FREQ, FXN_BIQUAD, FXN_COMPRESSOR, FXN_FREEVERB, FXN_CONV_REVERB = range(8)
 FXN_FDN_REVERB = 8
+FXN_DELAY, FXN_FLANGER = 9, 10
 MAX_PARENTS = 8
 
 FILTER_TYPES = ("filter", "filter-lowpass", "filter-highpass", "filter-bandpass", "filter-notch",
@@ -57,7 +59,8 @@ class _Node(C.Structure):
                 ("comp", C.POINTER(CompressorConfig)), ("verb", C.c_double * 5),
                 ("dyn_mode", C.c_int), ("dyn_range_db", C.c_double), ("dyn_hold_ms", C.c_double),
                 ("ir", C.POINTER(C.c_double)), ("ir_len", C.c_int64), ("conv_min_order", C.c_int),
-                ("conv_wet", C.c_double), ("conv_dry", C.c_double), ("fdn", C.POINTER(FdnConfig))]
+                ("conv_wet", C.c_double), ("conv_dry", C.c_double), ("fdn", C.POINTER(FdnConfig)),
+                ("delay", C.POINTER(DelayConfig)), ("flanger", C.POINTER(FlangerConfig))]
 
 
 def clamp(v, lo, hi):  # core.Clamp
@@ -218,6 +221,46 @@ def fdn_params(p: Params, fs: float) -> FdnConfig:
     c.damp = clamp(p.GetNum("damp", 0.45), 0, 0.99)
     c.mod_depth_seconds = clamp(p.GetNum("modDepth", 0.002), 0, 0.01)
     c.mod_rate_hz = clamp(p.GetNum("modRate", 0.1), 0, 1)
+    return c
+
+
+def _go_round(v: float) -> float:  # math.Round: halves away from zero
+    a = abs(v)
+    if a >= 2.0 ** 52:
+        return v
+    f = math.floor(a)
+    return math.copysign(f + 1 if a - f >= 0.5 else f, v)  # a - f is exact; a + 0.5 would round
+
+
+def delay_params(p: Params, fs: float) -> DelayConfig:
+    """delayRuntime.Configure (runtime_modulation.go:308-316): the clamped
+    values configureDelay (configure.go:329-346) hands to SetSampleRate(fs),
+    SetTargetTime, SetFeedback and SetMix of a NewDelay.  ad_delay_create
+    applies a config that way: the delay starts at round(0.25 fs) samples and
+    ramps to round(time * fs)."""
+    c = DelayConfig()
+    c.sample_rate = float(fs)
+    c.time_seconds = clamp(p.GetNum("time", 0.25), 0.001, 2)
+    c.feedback = clamp(p.GetNum("feedback", 0.35), 0, 0.99)
+    c.mix = clamp(p.GetNum("mix", 0.25), 0, 1)
+    return c
+
+
+def simple_delay_samples(p: Params, fs: float) -> int:
+    """simpleDelayRuntime.Configure (runtime_modulation.go:330-344): delaySamples."""
+    delay_ms = clamp(p.GetNum("delayMs", 20), 0, 500)
+    return max(int(_go_round(delay_ms * fs / 1000.0)), 0)
+
+
+def flanger_params(p: Params, fs: float) -> FlangerConfig:
+    """flangerRuntime.Configure (runtime_modulation.go:38-48)."""
+    c = FlangerConfig()
+    c.sample_rate = float(fs)
+    c.rate_hz = clamp(p.GetNum("rateHz", 0.25), 0.05, 5)
+    c.base_delay_seconds = clamp(p.GetNum("baseDelay", 0.001), 0.0001, 0.01)
+    c.depth_seconds = clamp(p.GetNum("depth", 0.0015), 0, 0.0099)
+    c.feedback = clamp(p.GetNum("feedback", 0.25), -0.99, 0.99)
+    c.mix = clamp(p.GetNum("mix", 0.5), 0, 1)
     return c
 
 
@@ -399,6 +442,29 @@ class Chain:
                 keep.append(cfg)
                 d.fdn = C.pointer(cfg)
                 sd.update(type="fdn", fdn={f: getattr(cfg, f) for f, _ in cfg._fields_})
+            elif t == "delay":
+                d.type = FXN_DELAY
+                cfg = delay_params(p, fs)
+                keep.append(cfg)
+                d.delay = C.pointer(cfg)
+                sd.update(type="delay", delay={f: getattr(cfg, f) for f, _ in cfg._fields_})
+            elif t == "delay-simple":
+                samples = simple_delay_samples(p, fs)
+                if samples == 0:
+                    d.type = FXN_PASS  # a one-slot buffer: Process returns at once (runtime_modulation.go:347-349)
+                    sd["type"] = "pass"
+                else:
+                    d.type = FXN_DELAY
+                    cfg = DelayConfig(sample_rate=fs, mode=1, delay_samples=samples)
+                    keep.append(cfg)
+                    d.delay = C.pointer(cfg)
+                    sd.update(type="delay", delay={f: getattr(cfg, f) for f, _ in cfg._fields_})
+            elif t == "flanger":
+                d.type = FXN_FLANGER
+                cfg = flanger_params(p, fs)
+                keep.append(cfg)
+                d.flanger = C.pointer(cfg)
+                sd.update(type="flanger", flanger={f: getattr(cfg, f) for f, _ in cfg._fields_})
             elif t in ("reverb-freeverb", "reverb"):  # reverbRuntime without model "fdn" is Freeverb
                 d.type = FXN_FREEVERB
                 for j, v in enumerate(freeverb_params(p)):

@@ -7,6 +7,8 @@ like the reference's own tests:
   dynamics.Compressor            dsp/effects/dynamics/compressor.go
   reverb.Reverb (Freeverb)       dsp/effects/reverb/reverb.go
   reverb.FDNReverb               dsp/effects/reverb/fdn_reverb.go
+  effects.Delay                  dsp/effects/delay.go
+  modulation.Flanger             dsp/effects/modulation/flanger.go
   fir.Filter                     dsp/filter/fir/filter.go
   effectchain filter -> dyn-compressor -> reverb-freeverb (EffectChain)
 
@@ -20,7 +22,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CompressorConfig, FdnConfig, check, f64, lib, ptr
+from ._lib import CompressorConfig, DelayConfig, FdnConfig, FlangerConfig, check, f64, lib, ptr
 
 DEVICE = 0
 SEC_STRIDE = 6  # {pre_gain, b0, b1, b2, a1, a2}
@@ -406,6 +408,197 @@ class FDNReverb:
             self.close()
         except Exception:
             pass
+
+
+class _Handle:
+    """A C handle with process / process_device / reset / destroy named ad_<kind>_*."""
+
+    _kind = ""
+
+    def _fn(self, name):
+        return getattr(lib(), f"ad_{self._kind}_{name}")
+
+    def ProcessInPlace(self, buf):
+        b = _as2d(buf, self.channels)
+        check(self._fn("process")(self._h, ptr(b), b.shape[1]))
+
+    def process_device(self, d_buf: int, stride: int, n: int, stream: int | None = None):
+        check(self._fn("process_device")(self._h, C.c_void_p(d_buf), int(stride), int(n), C.c_void_p(stream or 0)))
+
+    def Reset(self):
+        check(self._fn("reset")(self._h))
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Delay(_Handle):
+    """effects.Delay (delay.go:25-257) for `channels` instances sharing one
+    configuration: NewDelay(sample_rate), or `config` (a DelayConfig) as
+    ad_delay_create applies it (NewDelay, then SetTargetTime, SetFeedback,
+    SetMix; mode 1 is the graph's delay-simple).  The setters are the
+    reference's; a rejected value raises ErrInvalidArgument and changes nothing."""
+
+    P_SAMPLE_RATE, P_TIME, P_FEEDBACK, P_MIX, P_TARGET_TIME, P_SAMPLES, P_SMOOTH_COEFF = range(7)  # AD_DELAY_*
+    _kind = "delay"
+
+    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        cfg = DelayConfig()
+        if config is None:
+            lib().ad_delay_default_config(C.byref(cfg), float(sample_rate))
+        else:
+            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        check(lib().ad_delay_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+
+    def _set(self, which: int, v):
+        check(lib().ad_delay_set_param(self._h, which, float(v)))
+
+    def config(self) -> DelayConfig:
+        cfg = DelayConfig()
+        check(lib().ad_delay_get_config(self._h, C.byref(cfg)))
+        return cfg
+
+    def SetSampleRate(self, v):  # :63-72
+        self._set(self.P_SAMPLE_RATE, v)
+
+    def SetTime(self, v):  # :77-89
+        self._set(self.P_TIME, v)
+
+    def SetTargetTime(self, v):  # :95-106
+        self._set(self.P_TARGET_TIME, v)
+
+    def SetFeedback(self, v):  # :109-117
+        self._set(self.P_FEEDBACK, v)
+
+    def SetMix(self, v):  # :120-128
+        self._set(self.P_MIX, v)
+
+    def SetDelaySamples(self, v):  # mode 1: simpleDelayRuntime.Configure
+        self._set(self.P_SAMPLES, v)
+
+    def SetSmoothCoeff(self, v):  # smoothCoeff, for a caller whose exp is not the C library's
+        self._set(self.P_SMOOTH_COEFF, v)
+
+    def SampleRate(self) -> float:  # :176-185
+        return self.config().sample_rate
+
+    def Time(self) -> float:
+        return self.config().time_seconds
+
+    def Feedback(self) -> float:
+        return self.config().feedback
+
+    def Mix(self) -> float:
+        return self.config().mix
+
+    def derived(self):
+        """(currentSamples, targetSamples, ring length, write position) of ad_delay_derived."""
+        c, t, ln, wp = C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
+        check(lib().ad_delay_derived(self._h, C.byref(c), C.byref(t), C.byref(ln), C.byref(wp)))
+        return c.value, t.value, ln.value, wp.value
+
+    def CurrentDelaySamples(self) -> float:  # :189
+        return self.derived()[0]
+
+    def kernel_info(self):
+        """(block, sub_block, regime of the last call, its launches) of ad_delay_kernel_info."""
+        v = [C.c_int() for _ in range(4)]
+        check(lib().ad_delay_kernel_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def set_regime(self, regime: int):
+        """0: the library chooses; 1: one launch per block; 2: one persistent launch."""
+        check(lib().ad_delay_set_regime(self._h, int(regime)))
+
+
+class Flanger(_Handle):
+    """modulation.Flanger (flanger.go:108-424) for `channels` instances sharing
+    one configuration: NewFlanger(sample_rate, options...) with the options as
+    keywords (rate_hz, depth_seconds, base_delay_seconds, feedback, mix), or
+    `config` (a FlangerConfig) applied whole."""
+
+    P_SAMPLE_RATE, P_RATE, P_DEPTH, P_BASE_DELAY, P_FEEDBACK, P_MIX = range(6)  # AD_FLANGER_*
+    _kind = "flanger"
+
+    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        cfg = FlangerConfig()
+        if config is None:
+            lib().ad_flanger_default_config(C.byref(cfg), float(sample_rate))
+        else:
+            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        for k, v in options.items():
+            if k not in ("rate_hz", "depth_seconds", "base_delay_seconds", "feedback", "mix"):
+                raise TypeError(f"unknown flanger option {k!r}")
+            setattr(cfg, k, float(v))
+        check(lib().ad_flanger_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+
+    def _set(self, which: int, v):
+        check(lib().ad_flanger_set_param(self._h, which, float(v)))
+
+    def config(self) -> FlangerConfig:
+        cfg = FlangerConfig()
+        check(lib().ad_flanger_get_config(self._h, C.byref(cfg)))
+        return cfg
+
+    def SetSampleRate(self, v):  # :165-173
+        self._set(self.P_SAMPLE_RATE, v)
+
+    def SetRateHz(self, v):  # :176-184
+        self._set(self.P_RATE, v)
+
+    def SetDepthSeconds(self, v):  # :187-203
+        self._set(self.P_DEPTH, v)
+
+    def SetBaseDelaySeconds(self, v):  # :206-224
+        self._set(self.P_BASE_DELAY, v)
+
+    def SetFeedback(self, v):  # :227-235
+        self._set(self.P_FEEDBACK, v)
+
+    def SetMix(self, v):  # :238-246
+        self._set(self.P_MIX, v)
+
+    def SampleRate(self) -> float:  # :299-314
+        return self.config().sample_rate
+
+    def RateHz(self) -> float:
+        return self.config().rate_hz
+
+    def DepthSeconds(self) -> float:
+        return self.config().depth_seconds
+
+    def BaseDelaySeconds(self) -> float:
+        return self.config().base_delay_seconds
+
+    def Feedback(self) -> float:
+        return self.config().feedback
+
+    def Mix(self) -> float:
+        return self.config().mix
+
+    def derived(self):
+        """(ring length, maxDelay, write position, LFO phase after the last call) of ad_flanger_derived."""
+        ln, md, wp, ph = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
+        check(lib().ad_flanger_derived(self._h, C.byref(ln), C.byref(md), C.byref(wp), C.byref(ph)))
+        return ln.value, md.value, wp.value, ph.value
+
+    def kernel_info(self):
+        """(block, sub_block, channels per workgroup, lds_bytes) of ad_flanger_kernel_info."""
+        v = [C.c_int() for _ in range(4)]
+        check(lib().ad_flanger_kernel_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
 
 class EffectChain(_FxChain):

@@ -61,13 +61,25 @@ struct FdnDel {
 };
 using FdnPtr = std::unique_ptr<ad_fdn, FdnDel>;
 
+struct DelayDel {
+  void operator()(ad_delay* d) const { ad_delay_destroy(d); }
+};
+using DelayPtr = std::unique_ptr<ad_delay, DelayDel>;
+
+struct FlangerDel {
+  void operator()(ad_flanger* f) const { ad_flanger_destroy(f); }
+};
+using FlangerPtr = std::unique_ptr<ad_flanger, FlangerDel>;
+
 struct FxOp {
-  enum Kind { ZERO, COPY, MIX, CHAIN, CONV, FDN } kind;
-  int dst = -1;                 // buffer id (written; CHAIN / CONV / FDN: read and written in place)
+  enum Kind { ZERO, COPY, MIX, CHAIN, CONV, FDN, DELAY, FLANGER } kind;
+  int dst = -1;                 // buffer id (written; CHAIN and later kinds: read and written in place)
   std::vector<int> srcs;        // COPY / MIX: buffers read
   ad_fx_chain* chain = nullptr;   // CHAIN
   ad_conv* conv = nullptr;        // CONV (many-channel convolution reverb)
   ad_fdn* fdn = nullptr;          // FDN (many-channel FDN reverb)
+  ad_delay* delay = nullptr;      // DELAY (feedback delay, delay-simple)
+  ad_flanger* flanger = nullptr;  // FLANGER
   // schedule (see schedule()): lane 0 is the caller's stream
   int lane = 0;
   std::vector<int> waits;  // ops on other lanes this op waits for
@@ -95,6 +107,8 @@ struct ad_fx_graph {
   std::vector<ChainPtr> chains;
   std::vector<ConvPtr> convs;
   std::vector<FdnPtr> fdns;
+  std::vector<DelayPtr> delays;
+  std::vector<FlangerPtr> flangers;
   DevBuf<double> pool;   // buffers 1..nbuf-1, [nbuf-1][channels][cap]
   int64_t cap = 0;
   DevBuf<double> work;   // host-call staging
@@ -115,6 +129,8 @@ struct ad_fx_graph {
     chains.clear();
     convs.clear();
     fdns.clear();
+    delays.clear();
+    flangers.clear();
     if (stream) {
       (void)hipStreamSynchronize(stream);
       (void)lib_stream_destroy(stream);
@@ -159,7 +175,7 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, int n) {
   int out_node = -1;
   for (int i = 0; i < n; ++i) {
     const ad_fx_node& d = nodes[i];
-    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_FDN_REVERB)
+    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_FLANGER)
       AD_FAIL(AD_ERR_UNKNOWN_EFFECT, "fx graph: node type not supported by the GPU runtime");
     if (d.type == AD_FXN_INPUT && i != 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: more than one input node");
     if (d.type == AD_FXN_OUTPUT) {
@@ -184,6 +200,8 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, int n) {
     if (d.type == AD_FXN_CONV_REVERB && !d.bypassed && (!d.ir || d.ir_len <= 0))
       AD_FAIL(AD_ERR_EMPTY_IMPULSE_RESPONSE, "fx graph: reverb-conv node without an impulse response");
     if (d.type == AD_FXN_FDN_REVERB && !d.fdn) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: reverb-fdn node without config");
+    if (d.type == AD_FXN_DELAY && !d.delay) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: delay node without config");
+    if (d.type == AD_FXN_FLANGER && !d.flanger) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: flanger node without config");
     if (d.type == AD_FXN_COMPRESSOR && (d.dyn_mode < 0 || d.dyn_mode > 2))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: bad dynamics mode");
   }
@@ -257,6 +275,28 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, int n) {
       g->ops.push_back(op);
       continue;
     }
+    if (d.type == AD_FXN_DELAY) {
+      flush(g, gr);
+      ad_delay* dl = nullptr;
+      ck(ad_delay_create(d.delay, g->channels, g->device, &dl));
+      g->delays.emplace_back(dl);
+      FxOp op{FxOp::DELAY};
+      op.dst = b;
+      op.delay = dl;
+      g->ops.push_back(op);
+      continue;
+    }
+    if (d.type == AD_FXN_FLANGER) {
+      flush(g, gr);
+      ad_flanger* fl = nullptr;
+      ck(ad_flanger_create(d.flanger, g->channels, g->device, &fl));
+      g->flangers.emplace_back(fl);
+      FxOp op{FxOp::FLANGER};
+      op.dst = b;
+      op.flanger = fl;
+      g->ops.push_back(op);
+      continue;
+    }
     const int lvl = d.type == AD_FXN_BIQUAD ? 1 : (d.type == AD_FXN_COMPRESSOR ? 2 : 3);
     if (gr.open && (lvl < gr.level() || (lvl == gr.level() && lvl > 1))) flush(g, gr);
     gr.open = true;
@@ -296,7 +336,7 @@ void schedule(ad_fx_graph* g) {
   for (int i = 0; i < (int)g->ops.size(); ++i) {
     FxOp& op = g->ops[i];
     std::vector<int> reads = op.srcs;
-    if (op.kind == FxOp::CHAIN || op.kind == FxOp::CONV || op.kind == FxOp::FDN) reads.push_back(op.dst);
+    if (op.kind >= FxOp::CHAIN) reads.push_back(op.dst);  // the in-place kinds
     std::vector<int> deps;
     for (int b : reads)
       if (last_writer[b] >= 0) deps.push_back(last_writer[b]);
@@ -393,6 +433,12 @@ void run(ad_fx_graph* g, double* d0, int64_t stride0, int64_t n, hipStream_t s) 
       case FxOp::FDN:
         ck(ad_fdn_process_device(op.fdn, dst, st(op.dst), n, ls));
         break;
+      case FxOp::DELAY:
+        ck(ad_delay_process_device(op.delay, dst, st(op.dst), n, ls));
+        break;
+      case FxOp::FLANGER:
+        ck(ad_flanger_process_device(op.flanger, dst, st(op.dst), n, ls));
+        break;
     }
     if (op.signal) AD_HIP(hipEventRecord(g->op_ev[i], ls));
   }
@@ -470,6 +516,8 @@ int ad_fx_graph_reset(ad_fx_graph* g) {
     for (auto& c : g->chains) ck(ad_fx_chain_reset(c.get()));
     for (auto& c : g->convs) ck(ad_conv_reset(c.get()));
     for (auto& f : g->fdns) ck(ad_fdn_reset(f.get()));
+    for (auto& d : g->delays) ck(ad_delay_reset(d.get()));
+    for (auto& f : g->flangers) ck(ad_flanger_reset(f.get()));
   });
 }
 

@@ -1,5 +1,5 @@
 // Call ordering and the ping-pong delay line shared by the handles that may be
-// called on any stream (ad_conv, ad_fir, ad_resampler, ad_fdn).
+// called on any stream (ad_conv, ad_fir, ad_resampler, ad_fdn, ad_delay, ad_flanger).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -525,7 +525,12 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
  *   AD_FXN_CONV_REVERB reverb.ConvolutionReverb.ProcessInPlace (reverb-conv,
  *                      runtime_misc.go:61-67) on the many-channel partitioned engine;
  *   AD_FXN_FDN_REVERB  reverb.FDNReverb.ProcessInPlace (reverb-fdn,
- *                      runtime_filter_pitch_reverb.go:366-368) on the FDN kernel.
+ *                      runtime_filter_pitch_reverb.go:366-368) on the FDN kernel;
+ *   AD_FXN_DELAY       effects.Delay.ProcessInPlace (delay), or with *delay in
+ *                      mode 1 the integer delay of delay-simple
+ *                      (runtime_modulation.go:304-362);
+ *   AD_FXN_FLANGER     modulation.Flanger.ProcessInPlace (flanger,
+ *                      runtime_modulation.go:34-52).
  * The result is the output node's buffer.  Linear runs of in-place nodes fuse
  * into one launch (bit-identical, see capi_fxgraph.cpp).  Other node types
  * return AD_ERR_UNKNOWN_EFFECT; the configs are copied at create.          */
@@ -542,8 +547,12 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
 #define AD_FXN_FDN_REVERB 8 /* reverb-fdn, and reverb with model "fdn" (runtime_filter_pitch_reverb.go:347-395):
                                FDNReverb.ProcessInPlace configured by *fdn (ad_fdn_config, below), an op
                                of its own on the many-channel FDN kernel */
+#define AD_FXN_DELAY 9   /* delay and delay-simple: an ad_delay created from *delay (below), an op of its own */
+#define AD_FXN_FLANGER 10 /* flanger: an ad_flanger created from *flanger (below), an op of its own */
 #define AD_FX_MAX_PARENTS 8
 struct ad_fdn_config;
+struct ad_delay_config;
+struct ad_flanger_config;
 typedef struct ad_fx_node {
   int type;
   int bypassed;
@@ -564,6 +573,8 @@ typedef struct ad_fx_node {
   int conv_min_order;               /* CONV_REVERB: minBlockOrder (reverb-conv uses 7; maxBlockOrder 13) */
   double conv_wet, conv_dry;        /* CONV_REVERB: SetWetDry(wet, dry) (reverb-conv: wet param, dry 1.0) */
   const struct ad_fdn_config* fdn;  /* FDN_REVERB */
+  const struct ad_delay_config* delay;     /* DELAY */
+  const struct ad_flanger_config* flanger; /* FLANGER */
 } ad_fx_node;
 typedef struct ad_fx_graph ad_fx_graph;
 int ad_fx_graph_create(const ad_fx_node* nodes, int n_nodes, int channels, int device, ad_fx_graph** out);
@@ -711,6 +722,118 @@ int ad_fdn_process(ad_fdn* f, double* buf, int64_t n);
 int ad_fdn_process_device(ad_fdn* f, double* d_buf, int64_t stride, int64_t n, void* stream);
 int ad_fdn_reset(ad_fdn* f);
 void ad_fdn_destroy(ad_fdn* f);
+
+/* ---- effects.Delay (dsp/effects/delay.go) and the graph's delay-simple
+ * (dsp/effectchain/runtime_modulation.go:322-362) -----------------------------
+ * The feedback delay with a linearly interpolated read and a one-pole ramp of
+ * the delay time, for `channels` independent instances that share one
+ * configuration.  ProcessSample (:140-166) bit for bit: the ramp, readExact,
+ * floor, frac, the two-tap mix, the write-back and the output mix each rounded
+ * as the reference rounds them, no FMA.  The rings ([channels][ceil(2 fs) + 1])
+ * live in device memory.
+ * config: mode 0 is Delay.  `smooth_coeff` 0 derives 1 - exp(-1/(fs * 0.010))
+ *   (computeSmoothCoeff :255) with the host's exp; a caller whose exp differs
+ *   in the last place (Go's math.Exp may) passes its own value, in (0, 1].
+ *   get_config returns the coefficient in use.  mode 1 is delay-simple: only
+ *   `delay_samples` (0 .. 2^27) counts, out[n] = in[n - delay_samples] copied,
+ *   not computed (-0 and non-finite values pass unchanged); 0 leaves the
+ *   buffer alone.
+ * default_config: NewDelay's defaults (0.25 s, feedback 0.35, mix 0.25), mode 0.
+ * validate: the setters' ranges (:63-128, :191-199), host only: sample rate
+ *   > 0 and finite, time in [0.001, 2], feedback in [0, 0.99], mix in [0, 1];
+ *   also refused: a ring of more than 2^27 samples.
+ * create: validation, then the device (AD_ERR_NO_DEVICE without one).  Mode 0
+ *   is NewDelay(sample_rate) followed by SetTargetTime(time_seconds),
+ *   SetFeedback and SetMix, as the graph's configureDelay does: the delay
+ *   starts at max(1, round(0.25 fs)) samples and ramps to round(time * fs).
+ * set_param: SAMPLE_RATE is SetSampleRate (a ring whose length changes keeps
+ *   its newest min(old, new) samples ending at write - 1, write becomes 0; the
+ *   delay snaps to max(1, round(time * fs)); the coefficient is derived anew).
+ *   TIME is SetTime (snaps, no clamp to one sample), TARGET_TIME is
+ *   SetTargetTime (ramps), FEEDBACK and MIX store.  SMOOTH_COEFF replaces the
+ *   coefficient (a caller's own exp, after SAMPLE_RATE).  SAMPLES (mode 1 only) is
+ *   simpleDelayRuntime.Configure: another length is a zeroed ring.  A rejected
+ *   value changes nothing.
+ * derived: currentSamples after the last call, targetSamples, the ring's
+ *   length as allocated (mode 1: delay_samples slots) and the write position.
+ * kernel_info: `block` consecutive samples neither read each other's writes
+ *   nor overwrite what another still reads, for the delay now and its target;
+ *   `sub_block` is the persistent kernel's tile; `regime` and `launches` tell
+ *   what the last call ran: 1 = one launch per block, 2 = one persistent
+ *   launch (0 before the first call).  set_regime forces one (0: choose).
+ * process / process_device / reset: as ad_fdn's.  Reset (:131-137) zeroes the
+ *   rings and the write position and keeps currentSamples.                  */
+typedef struct ad_delay ad_delay;
+typedef struct ad_delay_config {
+  double sample_rate, time_seconds, feedback, mix, smooth_coeff;
+  int mode;              /* 0 Delay, 1 delay-simple */
+  int64_t delay_samples; /* mode 1 */
+} ad_delay_config;
+#define AD_DELAY_SAMPLE_RATE 0 /* SetSampleRate :63 */
+#define AD_DELAY_TIME 1        /* SetTime :77 */
+#define AD_DELAY_FEEDBACK 2    /* SetFeedback :109 */
+#define AD_DELAY_MIX 3         /* SetMix :120 */
+#define AD_DELAY_TARGET_TIME 4 /* SetTargetTime :95 */
+#define AD_DELAY_SAMPLES 5     /* mode 1: simpleDelayRuntime.Configure's delaySamples */
+#define AD_DELAY_SMOOTH_COEFF 6 /* the ramp's coefficient, in (0, 1]; SAMPLE_RATE derives it anew */
+void ad_delay_default_config(ad_delay_config* cfg, double sample_rate);
+int ad_delay_validate(const ad_delay_config* cfg);
+int ad_delay_create(const ad_delay_config* cfg, int channels, int device, ad_delay** out);
+int ad_delay_set_param(ad_delay* d, int which, double value);
+int ad_delay_get_config(const ad_delay* d, ad_delay_config* cfg);
+int ad_delay_derived(const ad_delay* d, double* current_samples, double* target_samples, int64_t* ring_len,
+                     int64_t* write_pos);
+int ad_delay_kernel_info(const ad_delay* d, int* block, int* sub_block, int* regime, int* launches);
+int ad_delay_set_regime(ad_delay* d, int regime);
+int ad_delay_process(ad_delay* d, double* buf, int64_t n);
+int ad_delay_process_device(ad_delay* d, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_delay_reset(ad_delay* d);
+void ad_delay_destroy(ad_delay* d);
+
+/* ---- modulation.Flanger (dsp/effects/modulation/flanger.go) -----------------
+ * The LFO-modulated Hermite delay with signed feedback, for `channels`
+ * instances sharing one configuration.  Process (:259-282) bit for bit in its
+ * operation order except for the sine of the LFO, which is the device math
+ * library's (with depth 0 the outputs are bit-identical); the LFO phase is
+ * the reference's sequence of rounded additions and wraps.  A channel's ring
+ * (max(ceil((base + depth) fs) + 3, 4) samples) is held in LDS during a call.
+ * default_config: defaultFlangerConfig (:9-13) at sample_rate.
+ * validate: validateParams (:317-350), host only, `base + depth > 0.01`
+ *   included; also refused: a ring of more than 4065 samples (sample rates
+ *   above about 400 kHz).
+ * set_param: the named setter; SAMPLE_RATE, DEPTH and BASE_DELAY run
+ *   reconfigureDelayLine (:352-390): a ring whose length changes keeps its
+ *   newest min(old, new) samples, write becomes 0, the phase stays.  A rejected
+ *   value changes nothing (the setters' rollbacks :187-224).
+ * derived: ring length, maxDelay, write position, and the LFO phase after the
+ *   last call (waits for it).  kernel_info: `block` = max(1, P - 1),
+ *   P = floor(max(1, base * fs)), consecutive samples read none of each other's
+ *   writes; a wave is a tile of 64 / sub_block channels x sub_block samples.
+ * process / process_device / reset: as ad_fdn's.  Reset (:249-256) also
+ *   zeroes the phase.                                                       */
+typedef struct ad_flanger ad_flanger;
+typedef struct ad_flanger_config {
+  double sample_rate, rate_hz, depth_seconds, base_delay_seconds, feedback, mix;
+} ad_flanger_config;
+#define AD_FLANGER_SAMPLE_RATE 0 /* SetSampleRate :165 */
+#define AD_FLANGER_RATE 1        /* SetRateHz :176 */
+#define AD_FLANGER_DEPTH 2       /* SetDepthSeconds :187 */
+#define AD_FLANGER_BASE_DELAY 3  /* SetBaseDelaySeconds :206 */
+#define AD_FLANGER_FEEDBACK 4    /* SetFeedback :227 */
+#define AD_FLANGER_MIX 5         /* SetMix :238 */
+void ad_flanger_default_config(ad_flanger_config* cfg, double sample_rate);
+int ad_flanger_validate(const ad_flanger_config* cfg);
+int ad_flanger_create(const ad_flanger_config* cfg, int channels, int device, ad_flanger** out);
+int ad_flanger_set_param(ad_flanger* f, int which, double value);
+int ad_flanger_get_config(const ad_flanger* f, ad_flanger_config* cfg);
+int ad_flanger_derived(const ad_flanger* f, int64_t* ring_len, int64_t* max_delay, int64_t* write_pos,
+                       double* lfo_phase);
+int ad_flanger_kernel_info(const ad_flanger* f, int* block, int* sub_block, int* channels_per_workgroup,
+                           int* lds_bytes);
+int ad_flanger_process(ad_flanger* f, double* buf, int64_t n);
+int ad_flanger_process_device(ad_flanger* f, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_flanger_reset(ad_flanger* f);
+void ad_flanger_destroy(ad_flanger* f);
 
 /* ---- spectral correlation / deconvolution (dsp/conv/correlate.go,
  * dsp/conv/deconvolve.go) --------------------------------------
