@@ -124,6 +124,25 @@ class FlangerConfig(C.Structure):
                                           "mix")]
 
 
+class PhaserConfig(C.Structure):
+    """ad_phaser_config (include/algodsp.h); field k is parameter AD_PHASER_* = k."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "rate_hz", "min_freq_hz", "max_freq_hz", "feedback", "mix")] + \
+               [("stages", C.c_int)]
+
+
+class TremoloConfig(C.Structure):
+    """ad_tremolo_config (include/algodsp.h); field k is parameter AD_TREMOLO_* = k."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "rate_hz", "depth", "smoothing_ms", "mix", "smoothing_coeff")]
+
+
+class RingModConfig(C.Structure):
+    """ad_ringmod_config (include/algodsp.h); field k is parameter AD_RINGMOD_* = k."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "carrier_hz", "mix")]
+
+
 class DeconvOptionsC(C.Structure):
     """ad_deconv_options (include/algodsp.h)."""
 
@@ -308,6 +327,11 @@ def _declare(L: C.CDLL) -> None:
         "ad_flanger_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
         "ad_flanger_reset": (C.c_int, [vp]),
         "ad_flanger_destroy": (None, [vp]),
+        "ad_fx_graph_create_ext": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+        "ad_phaser_set_range": (C.c_int, [vp, C.c_double, C.c_double]),
+        "ad_phaser_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
+        "ad_tremolo_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
+        "ad_ringmod_kernel_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p]),
         "ad_correlate_fft": (C.c_int, [c_double_p, i64, c_double_p, i64, c_double_p, C.c_int]),
         "ad_correlate_fft_device": (C.c_int, [vp, i64, vp, i64, vp, C.c_int, vp]),
         "ad_deconv_default_options": (DeconvOptionsC, []),
@@ -315,6 +339,19 @@ def _declare(L: C.CDLL) -> None:
                                     c_int64_p, C.c_int]),
         "ad_inverse_filter": (C.c_int, [c_double_p, i64, i64, C.c_double, c_double_p, C.c_int]),
     }
+    for kind, cfg in (("phaser", PhaserConfig), ("tremolo", TremoloConfig), ("ringmod", RingModConfig)):
+        sig.update({  # the three modulation handles share their prototypes
+            f"ad_{kind}_default_config": (None, [C.POINTER(cfg), C.c_double]),
+            f"ad_{kind}_validate": (C.c_int, [C.POINTER(cfg)]),
+            f"ad_{kind}_create": (C.c_int, [C.POINTER(cfg), C.c_int, C.c_int, C.POINTER(vp)]),
+            f"ad_{kind}_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
+            f"ad_{kind}_get_config": (C.c_int, [vp, C.POINTER(cfg)]),
+            f"ad_{kind}_peek_lfo": (C.c_int, [vp, i64, c_double_p, c_double_p]),
+            f"ad_{kind}_process": (C.c_int, [vp, c_double_p, i64]),
+            f"ad_{kind}_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
+            f"ad_{kind}_reset": (C.c_int, [vp]),
+            f"ad_{kind}_destroy": (None, [vp]),
+        })
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
         fn.restype = res

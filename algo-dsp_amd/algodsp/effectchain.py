@@ -14,9 +14,11 @@ chain_process.go:177-227 for split-freq).  The compiled node list goes to
 ad_fx_graph_create (include/algodsp.h), which runs every node on the GPU;
 there is no CPU path.  Node types outside {filter*, dyn-compressor,
 dyn-limiter, dyn-gate, dyn-expander, reverb-freeverb, reverb-fdn, reverb,
-reverb-conv, delay, delay-simple, flanger, split-freq, split, sum, _input,
-_output} raise
-UnknownEffect (the GPU runtime's ErrUnknownEffect).
+reverb-conv, delay, delay-simple, flanger, phaser, tremolo, ringmod, split-freq,
+split, sum, _input, _output} raise
+UnknownEffect (the GPU runtime's ErrUnknownEffect).  The phaser, tremolo and
+ringmod nodes carry their configuration in a parallel array (_NodeExt,
+ad_fx_graph_create_ext); _Node keeps its layout.
 """
 from __future__ import annotations
 
@@ -27,7 +29,8 @@ import math
 import numpy as np
 
 from . import design
-from ._lib import CompressorConfig, DelayConfig, FdnConfig, FlangerConfig, check, lib, ptr
+from ._lib import (CompressorConfig, DelayConfig, FdnConfig, FlangerConfig, PhaserConfig, RingModConfig, TremoloConfig,
+                   check, lib, ptr)
 from .processors import section_table
 
 INPUT_NODE_ID = "_input"  # graph.go:10-13
@@ -37,6 +40,7 @@ NODE_TYPE_SPLIT_FREQ = "split-freq"
 FXN_INPUT, FXN_OUTPUT, FXN_PASS, FXN_SPLIT_FREQ, FXN_BIQUAD, FXN_COMPRESSOR, FXN_FREEVERB, FXN_CONV_REVERB = range(8)
 FXN_FDN_REVERB = 8
 FXN_DELAY, FXN_FLANGER = 9, 10
+FXN_PHASER, FXN_TREMOLO, FXN_RINGMOD = 11, 12, 13
 MAX_PARENTS = 8
 
 FILTER_TYPES = ("filter", "filter-lowpass", "filter-highpass", "filter-bandpass", "filter-notch",
@@ -61,6 +65,13 @@ class _Node(C.Structure):
                 ("ir", C.POINTER(C.c_double)), ("ir_len", C.c_int64), ("conv_min_order", C.c_int),
                 ("conv_wet", C.c_double), ("conv_dry", C.c_double), ("fdn", C.POINTER(FdnConfig)),
                 ("delay", C.POINTER(DelayConfig)), ("flanger", C.POINTER(FlangerConfig))]
+
+
+class _NodeExt(C.Structure):
+    """ad_fx_node_ext: the configurations of the node types added after ad_fx_node was laid out."""
+
+    _fields_ = [("phaser", C.POINTER(PhaserConfig)), ("tremolo", C.POINTER(TremoloConfig)),
+                ("ringmod", C.POINTER(RingModConfig))]
 
 
 def clamp(v, lo, hi):  # core.Clamp
@@ -264,6 +275,42 @@ def flanger_params(p: Params, fs: float) -> FlangerConfig:
     return c
 
 
+def phaser_params(p: Params, fs: float) -> PhaserConfig:
+    """phaserRuntime.Configure (runtime_modulation.go:263-279): the clamped
+    values configurePhaser (configure.go:276-303) hands to the setters.  A
+    maxFreqHz that clamps to 0.49 fs itself fails validateParams there, as it
+    fails ad_phaser_validate here."""
+    c = PhaserConfig()
+    c.sample_rate = float(fs)
+    c.min_freq_hz = clamp(p.GetNum("minFreqHz", 300), 20, fs * 0.45)
+    c.max_freq_hz = clamp(p.GetNum("maxFreqHz", 1600), c.min_freq_hz + 1, fs * 0.49)
+    c.stages = min(max(int(_go_round(p.GetNum("stages", 6))), 1), 12)
+    c.rate_hz = clamp(p.GetNum("rateHz", 0.4), 0.05, 5)
+    c.feedback = clamp(p.GetNum("feedback", 0.2), -0.99, 0.99)
+    c.mix = clamp(p.GetNum("mix", 0.5), 0, 1)
+    return c
+
+
+def tremolo_params(p: Params, fs: float) -> TremoloConfig:
+    """tremoloRuntime.Configure (runtime_modulation.go:289-298); smoothing_coeff 0: the library derives it."""
+    c = TremoloConfig()
+    c.sample_rate = float(fs)
+    c.rate_hz = clamp(p.GetNum("rateHz", 4), 0.05, 20)
+    c.depth = clamp(p.GetNum("depth", 0.6), 0, 1)
+    c.smoothing_ms = clamp(p.GetNum("smoothingMs", 5), 0, 200)
+    c.mix = clamp(p.GetNum("mix", 1), 0, 1)
+    return c
+
+
+def ringmod_params(p: Params, fs: float) -> RingModConfig:
+    """ringModRuntime.Configure (runtime_modulation.go:58-65)."""
+    c = RingModConfig()
+    c.sample_rate = float(fs)
+    c.carrier_hz = clamp(p.GetNum("carrierHz", 440), 1, fs * 0.49)
+    c.mix = clamp(p.GetNum("mix", 1), 0, 1)
+    return c
+
+
 def _filter_kind(node_type, raw):  # normalizeFilterKind normalize.go:42-86
     k = raw.strip().lower()
     if k in ("bandeq", "band-eq", "bandeqpeak", "bell", "bandbell"):
@@ -373,6 +420,7 @@ class Chain:
         idx = {k: i for i, k in enumerate(order)}
         fs = self.sample_rate
         nodes = (_Node * len(order))()
+        ext = (_NodeExt * len(order))()
         keep = []
         spec = []
         for i, k in enumerate(order):
@@ -465,6 +513,30 @@ class Chain:
                 keep.append(cfg)
                 d.flanger = C.pointer(cfg)
                 sd.update(type="flanger", flanger={f: getattr(cfg, f) for f, _ in cfg._fields_})
+            elif t == "phaser":
+                d.type = FXN_PHASER
+                # the factory builds NewPhaser(fs) with its defaults first (registry_defaults.go:112-119): a
+                # sample rate with 1600 >= 0.49 fs fails there, before the node's own range is read
+                base = PhaserConfig()
+                lib().ad_phaser_default_config(C.byref(base), fs)
+                check(lib().ad_phaser_validate(C.byref(base)))
+                cfg = phaser_params(p, fs)
+                check(lib().ad_phaser_validate(C.byref(cfg)))
+                keep.append(cfg)
+                ext[i].phaser = C.pointer(cfg)
+                sd.update(type="phaser", phaser={f: getattr(cfg, f) for f, _ in cfg._fields_})
+            elif t == "tremolo":
+                d.type = FXN_TREMOLO
+                cfg = tremolo_params(p, fs)
+                keep.append(cfg)
+                ext[i].tremolo = C.pointer(cfg)
+                sd.update(type="tremolo", tremolo={f: getattr(cfg, f) for f, _ in cfg._fields_})
+            elif t == "ringmod":
+                d.type = FXN_RINGMOD
+                cfg = ringmod_params(p, fs)
+                keep.append(cfg)
+                ext[i].ringmod = C.pointer(cfg)
+                sd.update(type="ringmod", ringmod={f: getattr(cfg, f) for f, _ in cfg._fields_})
             elif t in ("reverb-freeverb", "reverb"):  # reverbRuntime without model "fdn" is Freeverb
                 d.type = FXN_FREEVERB
                 for j, v in enumerate(freeverb_params(p)):
@@ -487,7 +559,8 @@ class Chain:
                 raise UnknownEffect(f"effect type {t!r} is not run by the GPU graph runtime")
             spec.append(sd)
         h = C.c_void_p()
-        check(lib().ad_fx_graph_create(C.cast(nodes, C.c_void_p), len(order), self.channels, self.device, C.byref(h)))
+        check(lib().ad_fx_graph_create_ext(C.cast(nodes, C.c_void_p), C.cast(ext, C.c_void_p), len(order),
+                                           self.channels, self.device, C.byref(h)))
         self._h = h
         self._keep = keep
         self.spec = spec

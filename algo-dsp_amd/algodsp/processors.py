@@ -9,6 +9,9 @@ like the reference's own tests:
   reverb.FDNReverb               dsp/effects/reverb/fdn_reverb.go
   effects.Delay                  dsp/effects/delay.go
   modulation.Flanger             dsp/effects/modulation/flanger.go
+  modulation.Phaser              dsp/effects/modulation/phaser.go
+  modulation.Tremolo             dsp/effects/modulation/tremolo.go
+  modulation.RingModulator       dsp/effects/modulation/ring_modulator.go
   fir.Filter                     dsp/filter/fir/filter.go
   effectchain filter -> dyn-compressor -> reverb-freeverb (EffectChain)
 
@@ -22,7 +25,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CompressorConfig, DelayConfig, FdnConfig, FlangerConfig, check, f64, lib, ptr
+from ._lib import (CompressorConfig, DelayConfig, FdnConfig, FlangerConfig, PhaserConfig, RingModConfig, TremoloConfig,
+                   check, f64, lib, ptr)
 
 DEVICE = 0
 SEC_STRIDE = 6  # {pre_gain, b0, b1, b2, a1, a2}
@@ -599,6 +603,163 @@ class Flanger(_Handle):
         v = [C.c_int() for _ in range(4)]
         check(lib().ad_flanger_kernel_info(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+
+class _ModHandle(_Handle):
+    """What Phaser, Tremolo and RingModulator share: a config structure whose
+    field k is parameter k, options as keywords, and peek_lfo."""
+
+    _config = None
+    _options = ()
+
+    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        cfg = self._config()
+        if config is None:
+            self._fn("default_config")(C.byref(cfg), float(sample_rate))
+        else:
+            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        for k, v in options.items():
+            if k not in self._options:
+                raise TypeError(f"unknown {self._kind} option {k!r}")
+            setattr(cfg, k, int(v) if k == "stages" else float(v))
+        check(self._fn("create")(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+
+    def _set(self, which: int, v):
+        check(self._fn("set_param")(self._h, which, float(v)))
+
+    def config(self):
+        cfg = self._config()
+        check(self._fn("get_config")(self._h, C.byref(cfg)))
+        return cfg
+
+    def peek_lfo(self, n: int):
+        """(phases, table) of the next n samples as the kernels would take them:
+        the table is the phaser's allpass coefficient, the tremolo's gain or the
+        ring modulator's carrier.  Nothing advances; phases[0] is the phase state."""
+        ph, tab = np.empty(int(n)), np.empty(int(n))
+        check(self._fn("peek_lfo")(self._h, int(n), ptr(ph), ptr(tab)))
+        return ph, tab
+
+    def SetSampleRate(self, v):
+        self._set(0, v)
+
+    def SetMix(self, v):
+        self._set(self.P_MIX, v)
+
+    def SampleRate(self) -> float:
+        return self.config().sample_rate
+
+    def Mix(self) -> float:
+        return self.config().mix
+
+
+class Phaser(_ModHandle):
+    """modulation.Phaser (phaser.go:130-379) for `channels` instances sharing one
+    configuration: NewPhaser(sample_rate, options...) with the options as
+    keywords (rate_hz, min_freq_hz, max_freq_hz, stages, feedback, mix), or
+    `config` (a PhaserConfig) applied whole.  A rejected setter value raises
+    ErrInvalidArgument and changes nothing."""
+
+    P_SAMPLE_RATE, P_RATE, P_MIN_FREQ, P_MAX_FREQ, P_FEEDBACK, P_MIX, P_STAGES = range(7)  # AD_PHASER_*
+    _kind = "phaser"
+    _config = PhaserConfig
+    _options = ("rate_hz", "min_freq_hz", "max_freq_hz", "stages", "feedback", "mix")
+
+    def SetRateHz(self, v):  # :194-202
+        self._set(self.P_RATE, v)
+
+    def SetFrequencyRangeHz(self, min_freq_hz, max_freq_hz):  # :205-218
+        check(lib().ad_phaser_set_range(self._h, float(min_freq_hz), float(max_freq_hz)))
+
+    def SetStages(self, v):  # :221-233
+        self._set(self.P_STAGES, v)
+
+    def SetFeedback(self, v):  # :236-244
+        self._set(self.P_FEEDBACK, v)
+
+    def RateHz(self) -> float:  # :302-320
+        return self.config().rate_hz
+
+    def MinFrequencyHz(self) -> float:
+        return self.config().min_freq_hz
+
+    def MaxFrequencyHz(self) -> float:
+        return self.config().max_freq_hz
+
+    def Stages(self) -> int:
+        return self.config().stages
+
+    def Feedback(self) -> float:
+        return self.config().feedback
+
+    def kernel_info(self):
+        """(channels per workgroup, samples staged per chunk, lds_bytes) of ad_phaser_kernel_info."""
+        v = [C.c_int() for _ in range(3)]
+        check(lib().ad_phaser_kernel_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+
+class Tremolo(_ModHandle):
+    """modulation.Tremolo (tremolo.go:86-294): NewTremolo(sample_rate,
+    options...) with the options as keywords (rate_hz, depth, smoothing_ms,
+    mix), or `config` (a TremoloConfig) applied whole."""
+
+    P_SAMPLE_RATE, P_RATE, P_DEPTH, P_SMOOTHING, P_MIX, P_SMOOTHING_COEFF = range(6)  # AD_TREMOLO_*
+    _kind = "tremolo"
+    _config = TremoloConfig
+    _options = ("rate_hz", "depth", "smoothing_ms", "mix", "smoothing_coeff")
+
+    def SetRateHz(self, v):  # :150-158
+        self._set(self.P_RATE, v)
+
+    def SetDepth(self, v):  # :161-169
+        self._set(self.P_DEPTH, v)
+
+    def SetSmoothingMs(self, v):  # :172-181
+        self._set(self.P_SMOOTHING, v)
+
+    def SetSmoothingCoeff(self, v):  # smoothingCoef, for a caller whose exp is not the C library's
+        self._set(self.P_SMOOTHING_COEFF, v)
+
+    def RateHz(self) -> float:  # :233-246
+        return self.config().rate_hz
+
+    def Depth(self) -> float:
+        return self.config().depth
+
+    def SmoothingMs(self) -> float:
+        return self.config().smoothing_ms
+
+    def kernel_info(self):
+        """(samples of a row per apply workgroup, the stepper lane's chunk, smoothed) of ad_tremolo_kernel_info."""
+        v = [C.c_int() for _ in range(3)]
+        check(lib().ad_tremolo_kernel_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+
+class RingModulator(_ModHandle):
+    """modulation.RingModulator (ring_modulator.go:63-178):
+    NewRingModulator(sample_rate, options...) with the options as keywords
+    (carrier_hz, mix), or `config` (a RingModConfig) applied whole."""
+
+    P_SAMPLE_RATE, P_CARRIER, P_MIX = range(3)  # AD_RINGMOD_*
+    _kind = "ringmod"
+    _config = RingModConfig
+    _options = ("carrier_hz", "mix")
+
+    def SetCarrierHz(self, v):  # :115-124
+        self._set(self.P_CARRIER, v)
+
+    def CarrierHz(self) -> float:  # :171
+        return self.config().carrier_hz
+
+    def kernel_info(self):
+        """(samples of a row per apply workgroup, table threads, phaseInc) of ad_ringmod_kernel_info."""
+        a, b, inc = C.c_int(), C.c_int(), C.c_double()
+        check(lib().ad_ringmod_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(inc)))
+        return a.value, b.value, inc.value
 
 
 class EffectChain(_FxChain):

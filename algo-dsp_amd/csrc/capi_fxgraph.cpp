@@ -23,6 +23,8 @@
 //   * fan-in mixes are one kernel (k_fx_mix) in the reference's summation
 //     order; the split-freq low band runs in place on the node's buffer and
 //     the high band on a copy;
+//   * the reverbs other than Freeverb, the delays and the modulation effects
+//     (flanger, phaser, tremolo, ringmod) are ops of their own on their handles;
 //   * independent branches run concurrently on up to 8 streams (schedule()).
 #include <hip/hip_runtime.h>
 
@@ -71,8 +73,23 @@ struct FlangerDel {
 };
 using FlangerPtr = std::unique_ptr<ad_flanger, FlangerDel>;
 
+struct PhaserDel {
+  void operator()(ad_phaser* f) const { ad_phaser_destroy(f); }
+};
+using PhaserPtr = std::unique_ptr<ad_phaser, PhaserDel>;
+
+struct TremoloDel {
+  void operator()(ad_tremolo* f) const { ad_tremolo_destroy(f); }
+};
+using TremoloPtr = std::unique_ptr<ad_tremolo, TremoloDel>;
+
+struct RingmodDel {
+  void operator()(ad_ringmod* f) const { ad_ringmod_destroy(f); }
+};
+using RingmodPtr = std::unique_ptr<ad_ringmod, RingmodDel>;
+
 struct FxOp {
-  enum Kind { ZERO, COPY, MIX, CHAIN, CONV, FDN, DELAY, FLANGER } kind;
+  enum Kind { ZERO, COPY, MIX, CHAIN, CONV, FDN, DELAY, FLANGER, PHASER, TREMOLO, RINGMOD } kind;
   int dst = -1;                 // buffer id (written; CHAIN and later kinds: read and written in place)
   std::vector<int> srcs;        // COPY / MIX: buffers read
   ad_fx_chain* chain = nullptr;   // CHAIN
@@ -80,6 +97,9 @@ struct FxOp {
   ad_fdn* fdn = nullptr;          // FDN (many-channel FDN reverb)
   ad_delay* delay = nullptr;      // DELAY (feedback delay, delay-simple)
   ad_flanger* flanger = nullptr;  // FLANGER
+  ad_phaser* phaser = nullptr;    // PHASER
+  ad_tremolo* tremolo = nullptr;  // TREMOLO
+  ad_ringmod* ringmod = nullptr;  // RINGMOD
   // schedule (see schedule()): lane 0 is the caller's stream
   int lane = 0;
   std::vector<int> waits;  // ops on other lanes this op waits for
@@ -109,6 +129,9 @@ struct ad_fx_graph {
   std::vector<FdnPtr> fdns;
   std::vector<DelayPtr> delays;
   std::vector<FlangerPtr> flangers;
+  std::vector<PhaserPtr> phasers;
+  std::vector<TremoloPtr> tremolos;
+  std::vector<RingmodPtr> ringmods;
   DevBuf<double> pool;   // buffers 1..nbuf-1, [nbuf-1][channels][cap]
   int64_t cap = 0;
   DevBuf<double> work;   // host-call staging
@@ -131,6 +154,9 @@ struct ad_fx_graph {
     fdns.clear();
     delays.clear();
     flangers.clear();
+    phasers.clear();
+    tremolos.clear();
+    ringmods.clear();
     if (stream) {
       (void)hipStreamSynchronize(stream);
       (void)lib_stream_destroy(stream);
@@ -168,14 +194,14 @@ void flush(ad_fx_graph* g, Group& gr) {
   gr = Group{};
 }
 
-void compile(ad_fx_graph* g, const ad_fx_node* nodes, int n) {
+void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext, int n) {
   if (n < 2 || nodes[0].type != AD_FXN_INPUT) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: node 0 must be the input");
   // consumers of each (node, port)
   std::vector<int> uses((size_t)n * 2, 0);
   int out_node = -1;
   for (int i = 0; i < n; ++i) {
     const ad_fx_node& d = nodes[i];
-    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_FLANGER)
+    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_RINGMOD)
       AD_FAIL(AD_ERR_UNKNOWN_EFFECT, "fx graph: node type not supported by the GPU runtime");
     if (d.type == AD_FXN_INPUT && i != 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: more than one input node");
     if (d.type == AD_FXN_OUTPUT) {
@@ -202,6 +228,12 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, int n) {
     if (d.type == AD_FXN_FDN_REVERB && !d.fdn) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: reverb-fdn node without config");
     if (d.type == AD_FXN_DELAY && !d.delay) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: delay node without config");
     if (d.type == AD_FXN_FLANGER && !d.flanger) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: flanger node without config");
+    if (d.type == AD_FXN_PHASER && !(ext && ext[i].phaser))
+      AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: phaser node without config");
+    if (d.type == AD_FXN_TREMOLO && !(ext && ext[i].tremolo))
+      AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: tremolo node without config");
+    if (d.type == AD_FXN_RINGMOD && !(ext && ext[i].ringmod))
+      AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: ringmod node without config");
     if (d.type == AD_FXN_COMPRESSOR && (d.dyn_mode < 0 || d.dyn_mode > 2))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: bad dynamics mode");
   }
@@ -294,6 +326,39 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, int n) {
       FxOp op{FxOp::FLANGER};
       op.dst = b;
       op.flanger = fl;
+      g->ops.push_back(op);
+      continue;
+    }
+    if (d.type == AD_FXN_PHASER) {
+      flush(g, gr);
+      ad_phaser* ph = nullptr;
+      ck(ad_phaser_create(ext[i].phaser, g->channels, g->device, &ph));
+      g->phasers.emplace_back(ph);
+      FxOp op{FxOp::PHASER};
+      op.dst = b;
+      op.phaser = ph;
+      g->ops.push_back(op);
+      continue;
+    }
+    if (d.type == AD_FXN_TREMOLO) {
+      flush(g, gr);
+      ad_tremolo* tr = nullptr;
+      ck(ad_tremolo_create(ext[i].tremolo, g->channels, g->device, &tr));
+      g->tremolos.emplace_back(tr);
+      FxOp op{FxOp::TREMOLO};
+      op.dst = b;
+      op.tremolo = tr;
+      g->ops.push_back(op);
+      continue;
+    }
+    if (d.type == AD_FXN_RINGMOD) {
+      flush(g, gr);
+      ad_ringmod* rm = nullptr;
+      ck(ad_ringmod_create(ext[i].ringmod, g->channels, g->device, &rm));
+      g->ringmods.emplace_back(rm);
+      FxOp op{FxOp::RINGMOD};
+      op.dst = b;
+      op.ringmod = rm;
       g->ops.push_back(op);
       continue;
     }
@@ -439,6 +504,15 @@ void run(ad_fx_graph* g, double* d0, int64_t stride0, int64_t n, hipStream_t s) 
       case FxOp::FLANGER:
         ck(ad_flanger_process_device(op.flanger, dst, st(op.dst), n, ls));
         break;
+      case FxOp::PHASER:
+        ck(ad_phaser_process_device(op.phaser, dst, st(op.dst), n, ls));
+        break;
+      case FxOp::TREMOLO:
+        ck(ad_tremolo_process_device(op.tremolo, dst, st(op.dst), n, ls));
+        break;
+      case FxOp::RINGMOD:
+        ck(ad_ringmod_process_device(op.ringmod, dst, st(op.dst), n, ls));
+        break;
     }
     if (op.signal) AD_HIP(hipEventRecord(g->op_ev[i], ls));
   }
@@ -459,6 +533,11 @@ int graph_guard(ad_fx_graph* g, Fn&& fn) {
 extern "C" {
 
 int ad_fx_graph_create(const ad_fx_node* nodes, int n_nodes, int channels, int device, ad_fx_graph** out) {
+  return ad_fx_graph_create_ext(nodes, nullptr, n_nodes, channels, device, out);
+}
+
+int ad_fx_graph_create_ext(const ad_fx_node* nodes, const ad_fx_node_ext* ext, int n_nodes, int channels, int device,
+                           ad_fx_graph** out) {
   if (out) *out = nullptr;
   ad_fx_graph* raw = nullptr;
   const int rc = guard([&] {
@@ -470,7 +549,7 @@ int ad_fx_graph_create(const ad_fx_node* nodes, int n_nodes, int channels, int d
     g->device = dev;
     g->channels = channels;
     AD_HIP(lib_stream_create(&g->stream));
-    compile(g.get(), nodes, n_nodes);
+    compile(g.get(), nodes, ext, n_nodes);
     schedule(g.get());
     for (int l = 1; l < g->lanes_used; ++l) AD_HIP(lib_stream_create(&g->lane[l]));
     AD_HIP(hipEventCreateWithFlags(&g->start_ev, hipEventDisableTiming));
@@ -518,6 +597,9 @@ int ad_fx_graph_reset(ad_fx_graph* g) {
     for (auto& f : g->fdns) ck(ad_fdn_reset(f.get()));
     for (auto& d : g->delays) ck(ad_delay_reset(d.get()));
     for (auto& f : g->flangers) ck(ad_flanger_reset(f.get()));
+    for (auto& f : g->phasers) ck(ad_phaser_reset(f.get()));
+    for (auto& f : g->tremolos) ck(ad_tremolo_reset(f.get()));
+    for (auto& f : g->ringmods) ck(ad_ringmod_reset(f.get()));
   });
 }
 

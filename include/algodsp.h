@@ -530,7 +530,11 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
  *                      mode 1 the integer delay of delay-simple
  *                      (runtime_modulation.go:304-362);
  *   AD_FXN_FLANGER     modulation.Flanger.ProcessInPlace (flanger,
- *                      runtime_modulation.go:34-52).
+ *                      runtime_modulation.go:34-52);
+ *   AD_FXN_PHASER / AD_FXN_TREMOLO / AD_FXN_RINGMOD  the ProcessInPlace of
+ *                      modulation.Phaser, Tremolo and RingModulator (phaser,
+ *                      tremolo, ringmod, runtime_modulation.go:54-69, 259-302),
+ *                      configured through ad_fx_graph_create_ext.
  * The result is the output node's buffer.  Linear runs of in-place nodes fuse
  * into one launch (bit-identical, see capi_fxgraph.cpp).  Other node types
  * return AD_ERR_UNKNOWN_EFFECT; the configs are copied at create.          */
@@ -549,6 +553,9 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
                                of its own on the many-channel FDN kernel */
 #define AD_FXN_DELAY 9   /* delay and delay-simple: an ad_delay created from *delay (below), an op of its own */
 #define AD_FXN_FLANGER 10 /* flanger: an ad_flanger created from *flanger (below), an op of its own */
+#define AD_FXN_PHASER 11  /* phaser: an ad_phaser created from ext[i].phaser, an op of its own */
+#define AD_FXN_TREMOLO 12 /* tremolo: an ad_tremolo created from ext[i].tremolo, an op of its own */
+#define AD_FXN_RINGMOD 13 /* ringmod: an ad_ringmod created from ext[i].ringmod, an op of its own */
 #define AD_FX_MAX_PARENTS 8
 struct ad_fdn_config;
 struct ad_delay_config;
@@ -576,8 +583,21 @@ typedef struct ad_fx_node {
   const struct ad_delay_config* delay;     /* DELAY */
   const struct ad_flanger_config* flanger; /* FLANGER */
 } ad_fx_node;
+/* Configurations of the node types added after ad_fx_node was laid out; ext[i] belongs to nodes[i]. */
+struct ad_phaser_config;
+struct ad_tremolo_config;
+struct ad_ringmod_config;
+typedef struct ad_fx_node_ext {
+  const struct ad_phaser_config* phaser;   /* PHASER */
+  const struct ad_tremolo_config* tremolo; /* TREMOLO */
+  const struct ad_ringmod_config* ringmod; /* RINGMOD */
+} ad_fx_node_ext;
 typedef struct ad_fx_graph ad_fx_graph;
 int ad_fx_graph_create(const ad_fx_node* nodes, int n_nodes, int channels, int device, ad_fx_graph** out);
+/* The same with ext [n_nodes] (NULL: none, which is ad_fx_graph_create).  A PHASER, TREMOLO or RINGMOD
+ * node without its configuration is AD_ERR_INVALID_ARGUMENT, through either entry point. */
+int ad_fx_graph_create_ext(const ad_fx_node* nodes, const ad_fx_node_ext* ext, int n_nodes, int channels, int device,
+                           ad_fx_graph** out);
 /* buf [channels][n] (host) / [channels][stride] (device), processed in place. */
 int ad_fx_graph_process(ad_fx_graph* g, double* buf, int64_t n);
 int ad_fx_graph_process_device(ad_fx_graph* g, double* d_buf, int64_t stride, int64_t n, void* stream);
@@ -834,6 +854,108 @@ int ad_flanger_process(ad_flanger* f, double* buf, int64_t n);
 int ad_flanger_process_device(ad_flanger* f, double* d_buf, int64_t stride, int64_t n, void* stream);
 int ad_flanger_reset(ad_flanger* f);
 void ad_flanger_destroy(ad_flanger* f);
+
+/* ---- modulation.Phaser, Tremolo, RingModulator (dsp/effects/modulation/
+ * phaser.go, tremolo.go, ring_modulator.go) ----------------------------------
+ * For `channels` instances sharing one configuration.  The LFO (carrier) phase
+ * is one sequence for every channel: a call steps it on the host, the
+ * reference's rounded additions and wraps bit for bit, and the kernels take the
+ * sine once per sample.  Given that per-sample table (the phaser's allpass
+ * coefficient, the tremolo's gain currentMod, the ring modulator's carrier),
+ * Process is bit for bit the reference's operation order; the table itself
+ * differs from the reference by the device math library's sin and tan only
+ * (and is exact where it does not depend on them: tremolo depth 0).
+ * A config's field k is parameter k.
+ * default_config: the reference's defaults at sample_rate.
+ * validate: validateParams, host only.  Phaser: max_freq_hz < 0.49 sample_rate
+ *   strictly, stages in [1, 12].  Tremolo: smoothing_coeff is 0 (derive
+ *   1 - exp(-1 / ((ms / 1000) fs)) clamped to [0, 1] with the C library's exp, 1
+ *   for smoothing <= 0) or a caller's own coefficient in (0, 1].
+ * set_param: the named setter with its own check; a rejected value changes
+ *   nothing (the reference's phaser keeps a rejected sample rate or range; this
+ *   handle does not).  AD_PHASER_MIN_FREQ / MAX_FREQ are SetFrequencyRangeHz
+ *   with the other bound as it is, ad_phaser_set_range sets both at once.
+ *   AD_PHASER_STAGES: the same count keeps the stage states, another one zeroes
+ *   them and keeps the feedback sample and the phase (SetStages :221-233).
+ *   Tremolo SAMPLE_RATE and SMOOTHING derive the coefficient anew;
+ *   get_config reports the coefficient in use.  Ring modulator SAMPLE_RATE and
+ *   CARRIER recompute the stored increment 2 pi carrier / fs.
+ * peek_lfo: the phases of the next n samples and the table values the kernels
+ *   would use for them (host arrays [n]), by the device code a call runs;
+ *   nothing advances.  phase_out[0] is the handle's phase state.
+ * kernel_info: phaser: channels per workgroup (one per lane), samples staged
+ *   through LDS per chunk, LDS bytes.  Tremolo: samples of a row a workgroup
+ *   of the apply kernel covers, the stepper lane's chunk, whether the gain is
+ *   smoothed (coefficient < 1).  Ring modulator: the same first value, the
+ *   table kernel's threads, the stored phase increment.
+ * process / process_device / reset: as ad_fdn's.  Reset: phaser :258-265
+ *   (stages, feedback sample, phase), tremolo :195-198 (phase 0, gain 1), ring
+ *   modulator :138-140 (phase).                                              */
+typedef struct ad_phaser ad_phaser;
+typedef struct ad_phaser_config {
+  double sample_rate, rate_hz, min_freq_hz, max_freq_hz, feedback, mix;
+  int stages;
+} ad_phaser_config;
+#define AD_PHASER_SAMPLE_RATE 0 /* SetSampleRate :183 */
+#define AD_PHASER_RATE 1        /* SetRateHz :194 */
+#define AD_PHASER_MIN_FREQ 2    /* SetFrequencyRangeHz :205 */
+#define AD_PHASER_MAX_FREQ 3
+#define AD_PHASER_FEEDBACK 4    /* SetFeedback :236 */
+#define AD_PHASER_MIX 5         /* SetMix :247 */
+#define AD_PHASER_STAGES 6      /* SetStages :221 */
+void ad_phaser_default_config(ad_phaser_config* cfg, double sample_rate);
+int ad_phaser_validate(const ad_phaser_config* cfg);
+int ad_phaser_create(const ad_phaser_config* cfg, int channels, int device, ad_phaser** out);
+int ad_phaser_set_param(ad_phaser* p, int which, double value);
+int ad_phaser_set_range(ad_phaser* p, double min_freq_hz, double max_freq_hz);
+int ad_phaser_get_config(const ad_phaser* p, ad_phaser_config* cfg);
+int ad_phaser_kernel_info(const ad_phaser* p, int* channels_per_workgroup, int* tile, int* lds_bytes);
+int ad_phaser_peek_lfo(ad_phaser* p, int64_t n, double* phase_out, double* coef_out);
+int ad_phaser_process(ad_phaser* p, double* buf, int64_t n);
+int ad_phaser_process_device(ad_phaser* p, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_phaser_reset(ad_phaser* p);
+void ad_phaser_destroy(ad_phaser* p);
+
+typedef struct ad_tremolo ad_tremolo;
+typedef struct ad_tremolo_config {
+  double sample_rate, rate_hz, depth, smoothing_ms, mix, smoothing_coeff;
+} ad_tremolo_config;
+#define AD_TREMOLO_SAMPLE_RATE 0     /* SetSampleRate :138 */
+#define AD_TREMOLO_RATE 1            /* SetRateHz :150 */
+#define AD_TREMOLO_DEPTH 2           /* SetDepth :161 */
+#define AD_TREMOLO_SMOOTHING 3       /* SetSmoothingMs :172 */
+#define AD_TREMOLO_MIX 4             /* SetMix :184 */
+#define AD_TREMOLO_SMOOTHING_COEFF 5 /* smoothingCoef, in (0, 1]; SAMPLE_RATE and SMOOTHING derive it anew */
+void ad_tremolo_default_config(ad_tremolo_config* cfg, double sample_rate);
+int ad_tremolo_validate(const ad_tremolo_config* cfg);
+int ad_tremolo_create(const ad_tremolo_config* cfg, int channels, int device, ad_tremolo** out);
+int ad_tremolo_set_param(ad_tremolo* t, int which, double value);
+int ad_tremolo_get_config(const ad_tremolo* t, ad_tremolo_config* cfg);
+int ad_tremolo_kernel_info(const ad_tremolo* t, int* samples_per_workgroup, int* smooth_chunk, int* smoothed);
+int ad_tremolo_peek_lfo(ad_tremolo* t, int64_t n, double* phase_out, double* gain_out);
+int ad_tremolo_process(ad_tremolo* t, double* buf, int64_t n);
+int ad_tremolo_process_device(ad_tremolo* t, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_tremolo_reset(ad_tremolo* t);
+void ad_tremolo_destroy(ad_tremolo* t);
+
+typedef struct ad_ringmod ad_ringmod;
+typedef struct ad_ringmod_config {
+  double sample_rate, carrier_hz, mix;
+} ad_ringmod_config;
+#define AD_RINGMOD_SAMPLE_RATE 0 /* SetSampleRate :103 */
+#define AD_RINGMOD_CARRIER 1     /* SetCarrierHz :115 */
+#define AD_RINGMOD_MIX 2         /* SetMix :127 */
+void ad_ringmod_default_config(ad_ringmod_config* cfg, double sample_rate);
+int ad_ringmod_validate(const ad_ringmod_config* cfg);
+int ad_ringmod_create(const ad_ringmod_config* cfg, int channels, int device, ad_ringmod** out);
+int ad_ringmod_set_param(ad_ringmod* r, int which, double value);
+int ad_ringmod_get_config(const ad_ringmod* r, ad_ringmod_config* cfg);
+int ad_ringmod_kernel_info(const ad_ringmod* r, int* samples_per_workgroup, int* table_threads, double* phase_inc);
+int ad_ringmod_peek_lfo(ad_ringmod* r, int64_t n, double* phase_out, double* carrier_out);
+int ad_ringmod_process(ad_ringmod* r, double* buf, int64_t n);
+int ad_ringmod_process_device(ad_ringmod* r, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_ringmod_reset(ad_ringmod* r);
+void ad_ringmod_destroy(ad_ringmod* r);
 
 /* ---- spectral correlation / deconvolution (dsp/conv/correlate.go,
  * dsp/conv/deconvolve.go) --------------------------------------
