@@ -571,7 +571,12 @@ class FxGraph:
             elif t == "conv":  # ConvolutionReverb(kernel, minOrder) + SetWetDry (convolution.go:28-85)
                 self.rt.append(["conv", Partitioned(d["kernel"], d["min_order"], 13), d["wet"], d["dry"]])
             else:
-                self.rt.append([t])
+                self.rt.append(self.node_runtime(d))
+
+    def node_runtime(self, d):
+        """The runtime of a node type this class has no oracle for: [type], a
+        pass-through.  tests/fxgraph_ref.py returns [type, process] instead."""
+        return [d["type"]]
 
     def process(self, block):
         n = len(block)
@@ -614,4 +619,6 @@ class FxGraph:
             elif r[0] == "conv":
                 rev = r[1].process_block(dst)
                 buf[i] = r[3] * dst + r[2] * rev  # block[i] = dry*block[i] + wet*reverbOut[i]
+            elif len(r) > 1:  # node_runtime's [type, process]
+                buf[i] = r[1](dst)
         return buf[[i for i, d in enumerate(self.nodes) if d["type"] == "output"][0]]
