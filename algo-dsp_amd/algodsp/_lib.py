@@ -143,6 +143,27 @@ class RingModConfig(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("sample_rate", "carrier_hz", "mix")]
 
 
+class DistortionConfig(C.Structure):
+    """ad_distortion_config (include/algodsp.h); field k (0..7) is parameter AD_DISTORTION_* = k, the ints
+    are parameters 8..13 in their order."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "drive", "mix", "output_level", "clip_level", "shape", "bias",
+                                          "cheb_gain")] + [("cheb_weights", C.c_double * 16)] + \
+               [(n, C.c_int) for n in ("mode", "approx", "cheb_order", "cheb_harmonic", "cheb_invert", "cheb_dc_bypass")]
+
+
+class BitCrusherConfig(C.Structure):
+    """ad_bitcrusher_config (include/algodsp.h); field k is parameter AD_BITCRUSHER_* = k."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "bit_depth", "mix")] + [("downsample", C.c_int)]
+
+
+class FxNodeCfg(C.Structure):
+    """ad_fx_node_cfg: a node's own config structure and its size."""
+
+    _fields_ = [("config", C.c_void_p), ("bytes", C.c_int64)]
+
+
 class DeconvOptionsC(C.Structure):
     """ad_deconv_options (include/algodsp.h)."""
 
@@ -332,6 +353,13 @@ def _declare(L: C.CDLL) -> None:
         "ad_phaser_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
         "ad_tremolo_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
         "ad_ringmod_kernel_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), c_double_p]),
+        "ad_fx_graph_create_cfg": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+        "ad_distortion_set_weights": (C.c_int, [vp, c_double_p, C.c_int]),
+        "ad_distortion_derived": (C.c_int, [vp] + [c_double_p] * 4 + [C.POINTER(C.c_int)]),
+        "ad_distortion_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 4),
+        "ad_distortion_curve": (C.c_int, [vp, c_double_p, i64, c_double_p]),
+        "ad_bitcrusher_derived": (C.c_int, [vp, C.c_int, c_double_p, C.POINTER(C.c_int), c_double_p]),
+        "ad_bitcrusher_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
         "ad_correlate_fft": (C.c_int, [c_double_p, i64, c_double_p, i64, c_double_p, C.c_int]),
         "ad_correlate_fft_device": (C.c_int, [vp, i64, vp, i64, vp, C.c_int, vp]),
         "ad_deconv_default_options": (DeconvOptionsC, []),
@@ -347,6 +375,18 @@ def _declare(L: C.CDLL) -> None:
             f"ad_{kind}_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
             f"ad_{kind}_get_config": (C.c_int, [vp, C.POINTER(cfg)]),
             f"ad_{kind}_peek_lfo": (C.c_int, [vp, i64, c_double_p, c_double_p]),
+            f"ad_{kind}_process": (C.c_int, [vp, c_double_p, i64]),
+            f"ad_{kind}_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
+            f"ad_{kind}_reset": (C.c_int, [vp]),
+            f"ad_{kind}_destroy": (None, [vp]),
+        })
+    for kind, cfg in (("distortion", DistortionConfig), ("bitcrusher", BitCrusherConfig)):
+        sig.update({  # the two waveshaping handles share these prototypes
+            f"ad_{kind}_default_config": (None, [C.POINTER(cfg), C.c_double]),
+            f"ad_{kind}_validate": (C.c_int, [C.POINTER(cfg)]),
+            f"ad_{kind}_create": (C.c_int, [C.POINTER(cfg), C.c_int, C.c_int, C.POINTER(vp)]),
+            f"ad_{kind}_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
+            f"ad_{kind}_get_config": (C.c_int, [vp, C.POINTER(cfg)]),
             f"ad_{kind}_process": (C.c_int, [vp, c_double_p, i64]),
             f"ad_{kind}_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
             f"ad_{kind}_reset": (C.c_int, [vp]),

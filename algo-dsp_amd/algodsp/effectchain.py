@@ -14,11 +14,14 @@ chain_process.go:177-227 for split-freq).  The compiled node list goes to
 ad_fx_graph_create (include/algodsp.h), which runs every node on the GPU;
 there is no CPU path.  Node types outside {filter*, dyn-compressor,
 dyn-limiter, dyn-gate, dyn-expander, reverb-freeverb, reverb-fdn, reverb,
-reverb-conv, delay, delay-simple, flanger, phaser, tremolo, ringmod, split-freq,
-split, sum, _input, _output} raise
+reverb-conv, delay, delay-simple, flanger, phaser, tremolo, ringmod, distortion,
+dist-cheb, bitcrusher, split-freq, split, sum, _input, _output} raise
 UnknownEffect (the GPU runtime's ErrUnknownEffect).  The phaser, tremolo and
 ringmod nodes carry their configuration in a parallel array (_NodeExt,
-ad_fx_graph_create_ext); _Node keeps its layout.
+ad_fx_graph_create_ext); _Node keeps its layout.  The distortion, dist-cheb
+and bitcrusher nodes carry theirs as (structure, size) in a second parallel
+array (FxNodeCfg, ad_fx_graph_create_cfg), which later node types can use as
+it is.
 """
 from __future__ import annotations
 
@@ -29,8 +32,8 @@ import math
 import numpy as np
 
 from . import design
-from ._lib import (CompressorConfig, DelayConfig, FdnConfig, FlangerConfig, PhaserConfig, RingModConfig, TremoloConfig,
-                   check, lib, ptr)
+from ._lib import (BitCrusherConfig, CompressorConfig, DelayConfig, DistortionConfig, FdnConfig, FlangerConfig,
+                   FxNodeCfg, PhaserConfig, RingModConfig, TremoloConfig, check, lib, ptr)
 from .processors import section_table
 
 INPUT_NODE_ID = "_input"  # graph.go:10-13
@@ -41,6 +44,7 @@ FXN_INPUT, FXN_OUTPUT, FXN_PASS, FXN_SPLIT_FREQ, FXN_BIQUAD, FXN_COMPRESSOR, FXN
 FXN_FDN_REVERB = 8
 FXN_DELAY, FXN_FLANGER = 9, 10
 FXN_PHASER, FXN_TREMOLO, FXN_RINGMOD = 11, 12, 13
+FXN_DISTORTION, FXN_BITCRUSHER = 15, 16  # 14 is not assigned
 MAX_PARENTS = 8
 
 FILTER_TYPES = ("filter", "filter-lowpass", "filter-highpass", "filter-bandpass", "filter-notch",
@@ -311,6 +315,89 @@ def ringmod_params(p: Params, fs: float) -> RingModConfig:
     return c
 
 
+DISTORTION_MODES = ("softclip", "hardclip", "tanh", "waveshaper1", "waveshaper2", "waveshaper3", "waveshaper4",
+                    "waveshaper5", "waveshaper6", "waveshaper7", "waveshaper8", "saturate", "saturate2", "softsat",
+                    "chebyshev")  # DistortionMode distortion.go:36-52
+
+
+def _distortion_mode(raw) -> int:  # normalizeDistortionMode normalize.go:102-137: anything else is softclip
+    return DISTORTION_MODES.index(raw) if raw in DISTORTION_MODES else 0
+
+
+def _distortion_approx(raw) -> int:  # normalizeDistortionApproxMode normalize.go:139-148
+    return 1 if raw == "polynomial" else 0
+
+
+def _chebyshev_harmonic(raw) -> int:  # normalizeChebyshevHarmonicMode normalize.go:150-161
+    return {"odd": 1, "even": 2}.get(raw, 0)
+
+
+def adjust_chebyshev_order(order: int, harmonic: int) -> int:
+    """configureDistortion's order adjustment (configure.go:131-153): up to the
+    harmonic mode's parity, capped at 16, down to the parity again, at least 1."""
+    odd, even = harmonic == 1, harmonic == 2
+    if (odd and order % 2 == 0) or (even and order % 2 != 0):
+        order += 1
+    order = min(order, 16)
+    if (odd and order % 2 == 0) or (even and order % 2 != 0):
+        order -= 1
+    return max(order, 1)
+
+
+def _distortion_config(fs, mode, approx, drive, mix, output, clip, shape, bias, order, harmonic, invert, gain,
+                       dc_bypass) -> DistortionConfig:
+    """configureDistortion (configure.go:114-215): the values its setters end with."""
+    c = DistortionConfig()
+    c.sample_rate = float(fs)
+    c.mode, c.approx = mode, approx
+    c.drive, c.mix, c.output_level, c.clip_level, c.shape, c.bias = drive, mix, output, clip, shape, bias
+    c.cheb_order = adjust_chebyshev_order(order, harmonic)
+    c.cheb_harmonic, c.cheb_invert, c.cheb_gain, c.cheb_dc_bypass = harmonic, int(invert), gain, int(dc_bypass)
+    return c
+
+
+def distortion_params(p: Params, fs: float) -> DistortionConfig:
+    """distortionRuntime.Configure (runtime_modulation.go:95-116): order 3,
+    every harmonic, no inversion, gain 1, no DC bypass, no weights."""
+    return _distortion_config(fs, _distortion_mode(p.Str.get("mode")), _distortion_approx(p.Str.get("approx")),
+                              clamp(p.GetNum("drive", 1.8), 0.01, 20), clamp(p.GetNum("mix", 1.0), 0, 1),
+                              clamp(p.GetNum("output", 1.0), 0, 4), clamp(p.GetNum("clip", 1.0), 0.05, 1),
+                              clamp(p.GetNum("shape", 0.5), 0, 1), clamp(p.GetNum("bias", 0), -1, 1),
+                              3, 0, False, 1.0, False)
+
+
+def dist_cheb_params(p: Params, fs: float) -> DistortionConfig:
+    """distChebRuntime.Configure (runtime_modulation.go:126-167): Chebyshev
+    mode at clip 1, shape 0.5, bias 0, and the weights w1..w16 (GetNum drops a
+    non-finite one for 0, so SetChebyshevWeights cannot fail)."""
+    harmonic = _chebyshev_harmonic(p.Str.get("harmonic"))
+    order = min(max(int(_go_round(p.GetNum("order", 3))), 1), 16)
+    c = _distortion_config(fs, DISTORTION_MODES.index("chebyshev"), _distortion_approx(p.Str.get("approx")),
+                           clamp(p.GetNum("drive", 1.0), 0.01, 20), clamp(p.GetNum("mix", 1.0), 0, 1),
+                           clamp(p.GetNum("output", 1.0), 0, 4), 1.0, 0.5, 0.0, order, harmonic,
+                           p.GetNum("invert", 0) >= 0.5, clamp(p.GetNum("gain", 1.0), 0, 4),
+                           p.GetNum("dcBypass", 0) >= 0.5)
+    for k in range(16):
+        c.cheb_weights[k] = p.GetNum(f"w{k + 1}", 0)
+    return c
+
+
+def bitcrusher_params(p: Params, fs: float) -> BitCrusherConfig:
+    """bitCrusherRuntime.Configure (runtime_modulation.go:75-85)."""
+    c = BitCrusherConfig()
+    c.sample_rate = float(fs)
+    c.bit_depth = clamp(p.GetNum("bitDepth", 8), 1, 32)
+    c.downsample = min(max(int(_go_round(p.GetNum("downsample", 4))), 1), 256)
+    c.mix = clamp(p.GetNum("mix", 1), 0, 1)
+    return c
+
+
+def _config_dict(cfg) -> dict:
+    """A config structure's fields as plain data (arrays as lists)."""
+    return {f: (list(getattr(cfg, f)) if isinstance(getattr(cfg, f), C.Array) else getattr(cfg, f))
+            for f, _ in cfg._fields_}
+
+
 def _filter_kind(node_type, raw):  # normalizeFilterKind normalize.go:42-86
     k = raw.strip().lower()
     if k in ("bandeq", "band-eq", "bandeqpeak", "bell", "bandbell"):
@@ -421,6 +508,7 @@ class Chain:
         fs = self.sample_rate
         nodes = (_Node * len(order))()
         ext = (_NodeExt * len(order))()
+        cfgs = (FxNodeCfg * len(order))()
         keep = []
         spec = []
         for i, k in enumerate(order):
@@ -537,6 +625,20 @@ class Chain:
                 keep.append(cfg)
                 ext[i].ringmod = C.pointer(cfg)
                 sd.update(type="ringmod", ringmod={f: getattr(cfg, f) for f, _ in cfg._fields_})
+            elif t in ("distortion", "dist-cheb"):
+                d.type = FXN_DISTORTION
+                cfg = distortion_params(p, fs) if t == "distortion" else dist_cheb_params(p, fs)
+                check(lib().ad_distortion_validate(C.byref(cfg)))
+                keep.append(cfg)
+                cfgs[i].config, cfgs[i].bytes = C.addressof(cfg), C.sizeof(cfg)
+                sd.update(type="distortion", distortion=_config_dict(cfg))
+            elif t == "bitcrusher":
+                d.type = FXN_BITCRUSHER
+                cfg = bitcrusher_params(p, fs)
+                check(lib().ad_bitcrusher_validate(C.byref(cfg)))
+                keep.append(cfg)
+                cfgs[i].config, cfgs[i].bytes = C.addressof(cfg), C.sizeof(cfg)
+                sd.update(type="bitcrusher", bitcrusher=_config_dict(cfg))
             elif t in ("reverb-freeverb", "reverb"):  # reverbRuntime without model "fdn" is Freeverb
                 d.type = FXN_FREEVERB
                 for j, v in enumerate(freeverb_params(p)):
@@ -559,8 +661,8 @@ class Chain:
                 raise UnknownEffect(f"effect type {t!r} is not run by the GPU graph runtime")
             spec.append(sd)
         h = C.c_void_p()
-        check(lib().ad_fx_graph_create_ext(C.cast(nodes, C.c_void_p), C.cast(ext, C.c_void_p), len(order),
-                                           self.channels, self.device, C.byref(h)))
+        check(lib().ad_fx_graph_create_cfg(C.cast(nodes, C.c_void_p), C.cast(ext, C.c_void_p), C.cast(cfgs, C.c_void_p),
+                                           len(order), self.channels, self.device, C.byref(h)))
         self._h = h
         self._keep = keep
         self.spec = spec

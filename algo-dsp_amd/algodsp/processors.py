@@ -12,6 +12,8 @@ like the reference's own tests:
   modulation.Phaser              dsp/effects/modulation/phaser.go
   modulation.Tremolo             dsp/effects/modulation/tremolo.go
   modulation.RingModulator       dsp/effects/modulation/ring_modulator.go
+  effects.Distortion             dsp/effects/distortion.go
+  effects.BitCrusher             dsp/effects/bit_crusher.go
   fir.Filter                     dsp/filter/fir/filter.go
   effectchain filter -> dyn-compressor -> reverb-freeverb (EffectChain)
 
@@ -25,8 +27,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (CompressorConfig, DelayConfig, FdnConfig, FlangerConfig, PhaserConfig, RingModConfig, TremoloConfig,
-                   check, f64, lib, ptr)
+from ._lib import (BitCrusherConfig, CompressorConfig, DelayConfig, DistortionConfig, FdnConfig, FlangerConfig,
+                   PhaserConfig, RingModConfig, TremoloConfig, check, f64, lib, ptr)
 
 DEVICE = 0
 SEC_STRIDE = 6  # {pre_gain, b0, b1, b2, a1, a2}
@@ -760,6 +762,203 @@ class RingModulator(_ModHandle):
         a, b, inc = C.c_int(), C.c_int(), C.c_double()
         check(lib().ad_ringmod_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(inc)))
         return a.value, b.value, inc.value
+
+
+class _ShaperHandle(_Handle):
+    """What Distortion and BitCrusher share: a config structure, options as
+    keywords, set_param with the int parameters as whole numbers."""
+
+    _config = None
+    _options = ()
+    _int_options = ()
+
+    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        cfg = self._config()
+        if config is None:
+            self._fn("default_config")(C.byref(cfg), float(sample_rate))
+        else:
+            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        for k, v in options.items():
+            if k == "cheb_weights":
+                w = [float(x) for x in v]
+                if len(w) > 16:
+                    raise TypeError("at most 16 chebyshev weights")
+                cfg.cheb_weights = (C.c_double * 16)(*w)
+            elif k in self._int_options:
+                setattr(cfg, k, int(v))
+            elif k in self._options:
+                setattr(cfg, k, float(v))
+            else:
+                raise TypeError(f"unknown {self._kind} option {k!r}")
+        check(self._fn("create")(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+
+    def _set(self, which: int, v):
+        check(self._fn("set_param")(self._h, which, float(v)))
+
+    def config(self):
+        cfg = self._config()
+        check(self._fn("get_config")(self._h, C.byref(cfg)))
+        return cfg
+
+    def SetSampleRate(self, v):
+        self._set(0, v)
+
+    def SetMix(self, v):
+        self._set(self.P_MIX, v)
+
+    def SampleRate(self) -> float:
+        return self.config().sample_rate
+
+    def Mix(self) -> float:
+        return self.config().mix
+
+
+class Distortion(_ShaperHandle):
+    """effects.Distortion (distortion.go:296-797) for `channels` instances
+    sharing one configuration: NewDistortion(sample_rate, options...) with the
+    options as keywords (mode, approx, drive, mix, output_level, clip_level,
+    shape, bias, cheb_order, cheb_harmonic, cheb_invert, cheb_gain,
+    cheb_dc_bypass, cheb_weights), or `config` (a DistortionConfig) applied
+    whole.  A rejected setter value raises ErrInvalidArgument and changes
+    nothing."""
+
+    (P_SAMPLE_RATE, P_DRIVE, P_MIX, P_OUTPUT_LEVEL, P_CLIP_LEVEL, P_SHAPE, P_BIAS, P_CHEB_GAIN, P_MODE, P_APPROX,
+     P_CHEB_ORDER, P_CHEB_HARMONIC, P_CHEB_INVERT, P_CHEB_DC_BYPASS) = range(14)  # AD_DISTORTION_*
+    # DistortionMode :36-52, DistortionApproxMode :57-60, ChebyshevHarmonicMode :65-69
+    MODES = ("softclip", "hardclip", "tanh", "waveshaper1", "waveshaper2", "waveshaper3", "waveshaper4",
+             "waveshaper5", "waveshaper6", "waveshaper7", "waveshaper8", "saturate", "saturate2", "softsat", "chebyshev")
+    APPROX = ("exact", "polynomial")
+    HARMONICS = ("all", "odd", "even")
+    _kind = "distortion"
+    _config = DistortionConfig
+    _options = ("drive", "mix", "output_level", "clip_level", "shape", "bias", "cheb_gain")
+    _int_options = ("mode", "approx", "cheb_order", "cheb_harmonic", "cheb_invert", "cheb_dc_bypass")
+
+    def SetMode(self, v):  # :376-384
+        self._set(self.P_MODE, v)
+
+    def SetApproxMode(self, v):  # :387-395
+        self._set(self.P_APPROX, v)
+
+    def SetDrive(self, v):  # :398-406
+        self._set(self.P_DRIVE, v)
+
+    def SetOutputLevel(self, v):  # :420-429
+        self._set(self.P_OUTPUT_LEVEL, v)
+
+    def SetClipLevel(self, v):  # :432-441
+        self._set(self.P_CLIP_LEVEL, v)
+
+    def SetShape(self, v):  # :444-452
+        self._set(self.P_SHAPE, v)
+
+    def SetBias(self, v):  # :455-463
+        self._set(self.P_BIAS, v)
+
+    def SetChebyshevOrder(self, v):  # :466-474
+        self._set(self.P_CHEB_ORDER, v)
+
+    def SetChebyshevHarmonicMode(self, v):  # :477-485
+        self._set(self.P_CHEB_HARMONIC, v)
+
+    def SetChebyshevInvert(self, on: bool):  # :488-490
+        self._set(self.P_CHEB_INVERT, 1 if on else 0)
+
+    def SetChebyshevGainLevel(self, v):  # :493-502
+        self._set(self.P_CHEB_GAIN, v)
+
+    def SetChebyshevDCBypass(self, on: bool):  # :505-507
+        self._set(self.P_CHEB_DC_BYPASS, 1 if on else 0)
+
+    def SetChebyshevWeights(self, weights):  # :514-529
+        w = f64(weights).reshape(-1)
+        check(lib().ad_distortion_set_weights(self._h, ptr(w), int(w.size)))
+
+    def Mode(self) -> int:  # :567-588
+        return self.config().mode
+
+    def Drive(self) -> float:
+        return self.config().drive
+
+    def OutputLevel(self) -> float:
+        return self.config().output_level
+
+    def ClipLevel(self) -> float:
+        return self.config().clip_level
+
+    def Shape(self) -> float:
+        return self.config().shape
+
+    def Bias(self) -> float:
+        return self.config().bias
+
+    def ChebyshevOrder(self) -> int:
+        return self.config().cheb_order
+
+    def derived(self):
+        """dict(atan_scale=atan(1 + 4 shape), scale6=1 + 6 shape, scale2=1 + 2 shape, one_minus_mix,
+        weights_active) of ad_distortion_derived: the constants the host computes for the kernels."""
+        v = [C.c_double() for _ in range(4)]
+        w = C.c_int()
+        check(lib().ad_distortion_derived(self._h, *[C.byref(x) for x in v], C.byref(w)))
+        return dict(atan_scale=v[0].value, scale6=v[1].value, scale2=v[2].value, one_minus_mix=v[3].value,
+                    weights_active=bool(w.value))
+
+    def kernel_info(self):
+        """(samples of a row per pointwise workgroup; channels per workgroup, samples staged per chunk and
+        lds_bytes of the DC-bypass kernel) of ad_distortion_kernel_info."""
+        v = [C.c_int() for _ in range(4)]
+        check(lib().ad_distortion_kernel_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def curve(self, x):
+        """shapeSample(x) * outputLevel with the finite check, by the device
+        code a call runs: the transfer curve.  Nothing advances."""
+        xs = f64(x).reshape(-1)
+        wet = np.empty_like(xs)
+        check(lib().ad_distortion_curve(self._h, ptr(xs), int(xs.size), ptr(wet)))
+        return wet.reshape(np.shape(x))
+
+
+class BitCrusher(_ShaperHandle):
+    """effects.BitCrusher (bit_crusher.go:92-230): NewBitCrusher(sample_rate,
+    options...) with the options as keywords (bit_depth, downsample, mix), or
+    `config` (a BitCrusherConfig) applied whole.  Every channel has its own
+    hold value; the hold counter is one for all of them."""
+
+    P_SAMPLE_RATE, P_BIT_DEPTH, P_MIX, P_DOWNSAMPLE = range(4)  # AD_BITCRUSHER_*
+    _kind = "bitcrusher"
+    _config = BitCrusherConfig
+    _options = ("bit_depth", "mix")
+    _int_options = ("downsample",)
+
+    def SetBitDepth(self, v):  # :149-160
+        self._set(self.P_BIT_DEPTH, v)
+
+    def SetDownsample(self, v):  # :163-172
+        self._set(self.P_DOWNSAMPLE, v)
+
+    def BitDepth(self) -> float:  # :214-220
+        return self.config().bit_depth
+
+    def Downsample(self) -> int:
+        return self.config().downsample
+
+    def derived(self, channel: int = 0):
+        """dict(quant_levels, counter, hold_value) of ad_bitcrusher_derived: quantLevels = exp2(bitDepth - 1)
+        as the host computed it, holdCounter, and holdValue of `channel`."""
+        q, c, h = C.c_double(), C.c_int(), C.c_double()
+        check(lib().ad_bitcrusher_derived(self._h, int(channel), C.byref(q), C.byref(c), C.byref(h)))
+        return dict(quant_levels=q.value, counter=c.value, hold_value=h.value)
+
+    def kernel_info(self):
+        """(samples of a row per workgroup, the staged span of whole hold periods, lds_bytes) of
+        ad_bitcrusher_kernel_info."""
+        v = [C.c_int() for _ in range(3)]
+        check(lib().ad_bitcrusher_kernel_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
 
 class EffectChain(_FxChain):

@@ -24,7 +24,8 @@
 //     order; the split-freq low band runs in place on the node's buffer and
 //     the high band on a copy;
 //   * the reverbs other than Freeverb, the delays and the modulation effects
-//     (flanger, phaser, tremolo, ringmod) are ops of their own on their handles;
+//     (flanger, phaser, tremolo, ringmod) and the waveshapers (distortion,
+//     dist-cheb, bitcrusher) are ops of their own on their handles;
 //   * independent branches run concurrently on up to 8 streams (schedule()).
 #include <hip/hip_runtime.h>
 
@@ -88,8 +89,18 @@ struct RingmodDel {
 };
 using RingmodPtr = std::unique_ptr<ad_ringmod, RingmodDel>;
 
+struct DistortionDel {
+  void operator()(ad_distortion* f) const { ad_distortion_destroy(f); }
+};
+using DistortionPtr = std::unique_ptr<ad_distortion, DistortionDel>;
+
+struct BitcrusherDel {
+  void operator()(ad_bitcrusher* f) const { ad_bitcrusher_destroy(f); }
+};
+using BitcrusherPtr = std::unique_ptr<ad_bitcrusher, BitcrusherDel>;
+
 struct FxOp {
-  enum Kind { ZERO, COPY, MIX, CHAIN, CONV, FDN, DELAY, FLANGER, PHASER, TREMOLO, RINGMOD } kind;
+  enum Kind { ZERO, COPY, MIX, CHAIN, CONV, FDN, DELAY, FLANGER, PHASER, TREMOLO, RINGMOD, DISTORTION, BITCRUSHER } kind;
   int dst = -1;                 // buffer id (written; CHAIN and later kinds: read and written in place)
   std::vector<int> srcs;        // COPY / MIX: buffers read
   ad_fx_chain* chain = nullptr;   // CHAIN
@@ -100,6 +111,8 @@ struct FxOp {
   ad_phaser* phaser = nullptr;    // PHASER
   ad_tremolo* tremolo = nullptr;  // TREMOLO
   ad_ringmod* ringmod = nullptr;  // RINGMOD
+  ad_distortion* distortion = nullptr;  // DISTORTION
+  ad_bitcrusher* bitcrusher = nullptr;  // BITCRUSHER
   // schedule (see schedule()): lane 0 is the caller's stream
   int lane = 0;
   std::vector<int> waits;  // ops on other lanes this op waits for
@@ -132,6 +145,8 @@ struct ad_fx_graph {
   std::vector<PhaserPtr> phasers;
   std::vector<TremoloPtr> tremolos;
   std::vector<RingmodPtr> ringmods;
+  std::vector<DistortionPtr> distortions;
+  std::vector<BitcrusherPtr> bitcrushers;
   DevBuf<double> pool;   // buffers 1..nbuf-1, [nbuf-1][channels][cap]
   int64_t cap = 0;
   DevBuf<double> work;   // host-call staging
@@ -157,6 +172,8 @@ struct ad_fx_graph {
     phasers.clear();
     tremolos.clear();
     ringmods.clear();
+    distortions.clear();
+    bitcrushers.clear();
     if (stream) {
       (void)hipStreamSynchronize(stream);
       (void)lib_stream_destroy(stream);
@@ -194,14 +211,21 @@ void flush(ad_fx_graph* g, Group& gr) {
   gr = Group{};
 }
 
-void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext, int n) {
+// the configuration of node i when it is there in full: cfg[i] of the size of the node type's structure
+template <class Cfg>
+const Cfg* node_cfg(const ad_fx_node_cfg* cfg, int i) {
+  if (!cfg || !cfg[i].config || cfg[i].bytes != (int64_t)sizeof(Cfg)) return nullptr;
+  return static_cast<const Cfg*>(cfg[i].config);
+}
+
+void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext, const ad_fx_node_cfg* cfg, int n) {
   if (n < 2 || nodes[0].type != AD_FXN_INPUT) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: node 0 must be the input");
   // consumers of each (node, port)
   std::vector<int> uses((size_t)n * 2, 0);
   int out_node = -1;
   for (int i = 0; i < n; ++i) {
     const ad_fx_node& d = nodes[i];
-    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_RINGMOD)
+    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_BITCRUSHER || (d.type > AD_FXN_RINGMOD && d.type < AD_FXN_DISTORTION))
       AD_FAIL(AD_ERR_UNKNOWN_EFFECT, "fx graph: node type not supported by the GPU runtime");
     if (d.type == AD_FXN_INPUT && i != 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: more than one input node");
     if (d.type == AD_FXN_OUTPUT) {
@@ -234,6 +258,16 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: tremolo node without config");
     if (d.type == AD_FXN_RINGMOD && !(ext && ext[i].ringmod))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: ringmod node without config");
+    if (d.type == AD_FXN_DISTORTION) {
+      const ad_distortion_config* c = node_cfg<ad_distortion_config>(cfg, i);
+      if (!c || ad_distortion_validate(c) != AD_OK)
+        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: distortion node without a valid config of its size");
+    }
+    if (d.type == AD_FXN_BITCRUSHER) {
+      const ad_bitcrusher_config* c = node_cfg<ad_bitcrusher_config>(cfg, i);
+      if (!c || ad_bitcrusher_validate(c) != AD_OK)
+        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: bitcrusher node without a valid config of its size");
+    }
     if (d.type == AD_FXN_COMPRESSOR && (d.dyn_mode < 0 || d.dyn_mode > 2))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: bad dynamics mode");
   }
@@ -359,6 +393,28 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
       FxOp op{FxOp::RINGMOD};
       op.dst = b;
       op.ringmod = rm;
+      g->ops.push_back(op);
+      continue;
+    }
+    if (d.type == AD_FXN_DISTORTION) {
+      flush(g, gr);
+      ad_distortion* ds = nullptr;
+      ck(ad_distortion_create(node_cfg<ad_distortion_config>(cfg, i), g->channels, g->device, &ds));
+      g->distortions.emplace_back(ds);
+      FxOp op{FxOp::DISTORTION};
+      op.dst = b;
+      op.distortion = ds;
+      g->ops.push_back(op);
+      continue;
+    }
+    if (d.type == AD_FXN_BITCRUSHER) {
+      flush(g, gr);
+      ad_bitcrusher* bc = nullptr;
+      ck(ad_bitcrusher_create(node_cfg<ad_bitcrusher_config>(cfg, i), g->channels, g->device, &bc));
+      g->bitcrushers.emplace_back(bc);
+      FxOp op{FxOp::BITCRUSHER};
+      op.dst = b;
+      op.bitcrusher = bc;
       g->ops.push_back(op);
       continue;
     }
@@ -513,6 +569,12 @@ void run(ad_fx_graph* g, double* d0, int64_t stride0, int64_t n, hipStream_t s) 
       case FxOp::RINGMOD:
         ck(ad_ringmod_process_device(op.ringmod, dst, st(op.dst), n, ls));
         break;
+      case FxOp::DISTORTION:
+        ck(ad_distortion_process_device(op.distortion, dst, st(op.dst), n, ls));
+        break;
+      case FxOp::BITCRUSHER:
+        ck(ad_bitcrusher_process_device(op.bitcrusher, dst, st(op.dst), n, ls));
+        break;
     }
     if (op.signal) AD_HIP(hipEventRecord(g->op_ev[i], ls));
   }
@@ -538,6 +600,11 @@ int ad_fx_graph_create(const ad_fx_node* nodes, int n_nodes, int channels, int d
 
 int ad_fx_graph_create_ext(const ad_fx_node* nodes, const ad_fx_node_ext* ext, int n_nodes, int channels, int device,
                            ad_fx_graph** out) {
+  return ad_fx_graph_create_cfg(nodes, ext, nullptr, n_nodes, channels, device, out);
+}
+
+int ad_fx_graph_create_cfg(const ad_fx_node* nodes, const ad_fx_node_ext* ext, const ad_fx_node_cfg* cfg, int n_nodes,
+                           int channels, int device, ad_fx_graph** out) {
   if (out) *out = nullptr;
   ad_fx_graph* raw = nullptr;
   const int rc = guard([&] {
@@ -549,7 +616,7 @@ int ad_fx_graph_create_ext(const ad_fx_node* nodes, const ad_fx_node_ext* ext, i
     g->device = dev;
     g->channels = channels;
     AD_HIP(lib_stream_create(&g->stream));
-    compile(g.get(), nodes, ext, n_nodes);
+    compile(g.get(), nodes, ext, cfg, n_nodes);
     schedule(g.get());
     for (int l = 1; l < g->lanes_used; ++l) AD_HIP(lib_stream_create(&g->lane[l]));
     AD_HIP(hipEventCreateWithFlags(&g->start_ev, hipEventDisableTiming));
@@ -600,6 +667,8 @@ int ad_fx_graph_reset(ad_fx_graph* g) {
     for (auto& f : g->phasers) ck(ad_phaser_reset(f.get()));
     for (auto& f : g->tremolos) ck(ad_tremolo_reset(f.get()));
     for (auto& f : g->ringmods) ck(ad_ringmod_reset(f.get()));
+    for (auto& f : g->distortions) ck(ad_distortion_reset(f.get()));
+    for (auto& f : g->bitcrushers) ck(ad_bitcrusher_reset(f.get()));
   });
 }
 

@@ -534,7 +534,12 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
  *   AD_FXN_PHASER / AD_FXN_TREMOLO / AD_FXN_RINGMOD  the ProcessInPlace of
  *                      modulation.Phaser, Tremolo and RingModulator (phaser,
  *                      tremolo, ringmod, runtime_modulation.go:54-69, 259-302),
- *                      configured through ad_fx_graph_create_ext.
+ *                      configured through ad_fx_graph_create_ext;
+ *   AD_FXN_DISTORTION  effects.Distortion.ProcessInPlace (distortion and
+ *                      dist-cheb, runtime_modulation.go:91-171) and
+ *   AD_FXN_BITCRUSHER  effects.BitCrusher.ProcessInPlace (bitcrusher,
+ *                      runtime_modulation.go:71-89), configured through
+ *                      ad_fx_graph_create_cfg.
  * The result is the output node's buffer.  Linear runs of in-place nodes fuse
  * into one launch (bit-identical, see capi_fxgraph.cpp).  Other node types
  * return AD_ERR_UNKNOWN_EFFECT; the configs are copied at create.          */
@@ -556,6 +561,9 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
 #define AD_FXN_PHASER 11  /* phaser: an ad_phaser created from ext[i].phaser, an op of its own */
 #define AD_FXN_TREMOLO 12 /* tremolo: an ad_tremolo created from ext[i].tremolo, an op of its own */
 #define AD_FXN_RINGMOD 13 /* ringmod: an ad_ringmod created from ext[i].ringmod, an op of its own */
+/* 14 is not assigned: it stays AD_ERR_UNKNOWN_EFFECT */
+#define AD_FXN_DISTORTION 15 /* distortion and dist-cheb: an ad_distortion created from cfg[i], an op of its own */
+#define AD_FXN_BITCRUSHER 16 /* bitcrusher: an ad_bitcrusher created from cfg[i], an op of its own */
 #define AD_FX_MAX_PARENTS 8
 struct ad_fdn_config;
 struct ad_delay_config;
@@ -598,6 +606,18 @@ int ad_fx_graph_create(const ad_fx_node* nodes, int n_nodes, int channels, int d
  * node without its configuration is AD_ERR_INVALID_ARGUMENT, through either entry point. */
 int ad_fx_graph_create_ext(const ad_fx_node* nodes, const ad_fx_node_ext* ext, int n_nodes, int channels, int device,
                            ad_fx_graph** out);
+/* The configuration transport of the node types after RINGMOD: cfg[i] belongs to nodes[i] and holds the
+ * node type's own config structure (DISTORTION: ad_distortion_config, BITCRUSHER: ad_bitcrusher_config) with
+ * its size, so a later node type needs neither a new structure nor a new entry point.  cfg NULL: none, which
+ * is ad_fx_graph_create_ext.  A DISTORTION or BITCRUSHER node without its configuration, with bytes other
+ * than the size of its structure, or with a configuration its validate refuses is AD_ERR_INVALID_ARGUMENT,
+ * through all three entry points.  The configurations are copied at create. */
+typedef struct ad_fx_node_cfg {
+  const void* config;
+  int64_t bytes;
+} ad_fx_node_cfg;
+int ad_fx_graph_create_cfg(const ad_fx_node* nodes, const ad_fx_node_ext* ext, const ad_fx_node_cfg* cfg, int n_nodes,
+                           int channels, int device, ad_fx_graph** out);
 /* buf [channels][n] (host) / [channels][stride] (device), processed in place. */
 int ad_fx_graph_process(ad_fx_graph* g, double* buf, int64_t n);
 int ad_fx_graph_process_device(ad_fx_graph* g, double* d_buf, int64_t stride, int64_t n, void* stream);
@@ -956,6 +976,104 @@ int ad_ringmod_process(ad_ringmod* r, double* buf, int64_t n);
 int ad_ringmod_process_device(ad_ringmod* r, double* d_buf, int64_t stride, int64_t n, void* stream);
 int ad_ringmod_reset(ad_ringmod* r);
 void ad_ringmod_destroy(ad_ringmod* r);
+
+/* ---- effects.Distortion, effects.BitCrusher (dsp/effects/distortion.go,
+ * bit_crusher.go) -------------------------------------------------------------
+ * For `channels` instances sharing one configuration.  Both are time-parallel:
+ * the distortion is pointwise (its Chebyshev DC bypass, a one-pole recurrence
+ * per channel, is the one serial path), the bit crusher is a sample-and-hold
+ * whose update positions follow from a counter that is the same for every
+ * channel, kept on the host.  Every expression is evaluated in the reference's
+ * written order, each operation rounded on its own, the clamps as the two
+ * comparisons the reference writes (a NaN passes them and is zeroed by the
+ * finite check).  So the modes made of + - * / (SoftClip, HardClip,
+ * Waveshaper1-4 and 6, Saturate, Saturate2, Chebyshev; with the polynomial
+ * approximation also Tanh, Waveshaper7 and SoftSat) and the bit crusher are
+ * bit for bit the reference's; the exact Tanh, Waveshaper5, 7, 8 and SoftSat
+ * differ from it by the device math library's tanh, atan and exp only, and
+ * Process is bit for bit in (1 - mix) + curve mix given ad_distortion_curve.
+ * Constants the reference recomputes per sample are computed once on the host
+ * with the C library: atan(1 + 4 shape), 1 + 6 shape, 1 + 2 shape, 1 - mix,
+ * quantLevels = exp2(bitDepth - 1).
+ * ad_distortion_config: field k (0..7) is parameter k; mode is DistortionMode
+ *   (distortion.go:36-52, 0..14), approx 0 exact / 1 polynomial, cheb_harmonic
+ *   0 all / 1 odd / 2 even, cheb_invert and cheb_dc_bypass 0 or 1.
+ * validate: the setters' own ranges (distortion.go:364-529, bit_crusher.go:
+ *   137-183) and validateChebyshevParity, host only.
+ * set_param: the named setter with its own check; the int parameters take a
+ *   whole number.  A rejected value changes nothing: the reference's
+ *   SetChebyshevOrder and SetChebyshevHarmonicMode keep a value that fails the
+ *   parity rule; these handles do not.  No setter clears state.
+ * ad_distortion_set_weights: SetChebyshevWeights :514-529, n <= 16 finite
+ *   values, the other slots zeroed.  Weights are active when one of the first
+ *   cheb_order slots is nonzero (:690-695).
+ * ad_distortion_curve: wet[i] = shapeSample(x[i]) * outputLevel, 0 where that
+ *   is not finite, for host arrays [n], by the device code a call runs (x is
+ *   the shaper's argument, after bias and drive).  Nothing advances.
+ * derived: the host-computed constants above and whether weights are active;
+ *   bit crusher: quantLevels, holdCounter and holdValue of `channel`.
+ * kernel_info: distortion: samples of a row a workgroup of the pointwise
+ *   kernel covers; channels per workgroup, samples staged per chunk and LDS
+ *   bytes of the DC-bypass kernel.  Bit crusher: samples of a row a workgroup
+ *   covers, the span of whole hold periods it stages (0 at downsample 1), its
+ *   LDS bytes.
+ * process / process_device / reset: as ad_fdn's.  Reset: distortion :532-535
+ *   (the two DC states), bit crusher :186-189 (counter 0, hold 0).           */
+typedef struct ad_distortion ad_distortion;
+typedef struct ad_distortion_config {
+  double sample_rate, drive, mix, output_level, clip_level, shape, bias, cheb_gain, cheb_weights[16];
+  int mode, approx, cheb_order, cheb_harmonic, cheb_invert, cheb_dc_bypass;
+} ad_distortion_config;
+#define AD_DISTORTION_SAMPLE_RATE 0     /* SetSampleRate :365 */
+#define AD_DISTORTION_DRIVE 1           /* SetDrive :398 */
+#define AD_DISTORTION_MIX 2             /* SetMix :409 */
+#define AD_DISTORTION_OUTPUT_LEVEL 3    /* SetOutputLevel :420 */
+#define AD_DISTORTION_CLIP_LEVEL 4      /* SetClipLevel :432 */
+#define AD_DISTORTION_SHAPE 5           /* SetShape :444 */
+#define AD_DISTORTION_BIAS 6            /* SetBias :455 */
+#define AD_DISTORTION_CHEB_GAIN 7       /* SetChebyshevGainLevel :493 */
+#define AD_DISTORTION_MODE 8            /* SetMode :376 */
+#define AD_DISTORTION_APPROX 9          /* SetApproxMode :387 */
+#define AD_DISTORTION_CHEB_ORDER 10     /* SetChebyshevOrder :466 */
+#define AD_DISTORTION_CHEB_HARMONIC 11  /* SetChebyshevHarmonicMode :477 */
+#define AD_DISTORTION_CHEB_INVERT 12    /* SetChebyshevInvert :488 */
+#define AD_DISTORTION_CHEB_DC_BYPASS 13 /* SetChebyshevDCBypass :505 */
+void ad_distortion_default_config(ad_distortion_config* cfg, double sample_rate);
+int ad_distortion_validate(const ad_distortion_config* cfg);
+int ad_distortion_create(const ad_distortion_config* cfg, int channels, int device, ad_distortion** out);
+int ad_distortion_set_param(ad_distortion* d, int which, double value);
+int ad_distortion_set_weights(ad_distortion* d, const double* w, int n);
+int ad_distortion_get_config(const ad_distortion* d, ad_distortion_config* cfg);
+int ad_distortion_derived(const ad_distortion* d, double* atan_scale, double* scale6, double* scale2,
+                          double* one_minus_mix, int* weights_active);
+int ad_distortion_kernel_info(const ad_distortion* d, int* samples_per_workgroup, int* dc_channels_per_workgroup,
+                              int* dc_tile, int* dc_lds_bytes);
+int ad_distortion_curve(ad_distortion* d, const double* x, int64_t n, double* wet);
+int ad_distortion_process(ad_distortion* d, double* buf, int64_t n);
+int ad_distortion_process_device(ad_distortion* d, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_distortion_reset(ad_distortion* d);
+void ad_distortion_destroy(ad_distortion* d);
+
+typedef struct ad_bitcrusher ad_bitcrusher;
+typedef struct ad_bitcrusher_config {
+  double sample_rate, bit_depth, mix;
+  int downsample;
+} ad_bitcrusher_config;
+#define AD_BITCRUSHER_SAMPLE_RATE 0 /* SetSampleRate :138 */
+#define AD_BITCRUSHER_BIT_DEPTH 1   /* SetBitDepth :149 */
+#define AD_BITCRUSHER_MIX 2         /* SetMix :175 */
+#define AD_BITCRUSHER_DOWNSAMPLE 3  /* SetDownsample :163 */
+void ad_bitcrusher_default_config(ad_bitcrusher_config* cfg, double sample_rate);
+int ad_bitcrusher_validate(const ad_bitcrusher_config* cfg);
+int ad_bitcrusher_create(const ad_bitcrusher_config* cfg, int channels, int device, ad_bitcrusher** out);
+int ad_bitcrusher_set_param(ad_bitcrusher* b, int which, double value);
+int ad_bitcrusher_get_config(const ad_bitcrusher* b, ad_bitcrusher_config* cfg);
+int ad_bitcrusher_derived(ad_bitcrusher* b, int channel, double* quant_levels, int* counter, double* hold_value);
+int ad_bitcrusher_kernel_info(const ad_bitcrusher* b, int* samples_per_workgroup, int* span, int* lds_bytes);
+int ad_bitcrusher_process(ad_bitcrusher* b, double* buf, int64_t n);
+int ad_bitcrusher_process_device(ad_bitcrusher* b, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_bitcrusher_reset(ad_bitcrusher* b);
+void ad_bitcrusher_destroy(ad_bitcrusher* b);
 
 /* ---- spectral correlation / deconvolution (dsp/conv/correlate.go,
  * dsp/conv/deconvolve.go) --------------------------------------
