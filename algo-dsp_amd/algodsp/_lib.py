@@ -200,6 +200,9 @@ def lib() -> C.CDLL:
     return _lib
 
 
+_NEWEST = ("ad_conv_multi_set_long_blocks", "ad_conv_multi_get_long_blocks")
+
+
 def _declare(L: C.CDLL) -> None:
     vp = C.c_void_p
     i64 = C.c_int64
@@ -241,6 +244,8 @@ def _declare(L: C.CDLL) -> None:
         "ad_conv_multi_set_schedule": (C.c_int, [vp, C.c_int, i64, i64]),
         "ad_conv_lowlat_stats": (C.c_int, [vp, c_int64_p, c_int64_p]),
         "ad_conv_multi_get_schedule": (C.c_int, [vp, C.POINTER(C.c_int), c_int64_p]),
+        "ad_conv_multi_set_long_blocks": (C.c_int, [vp, C.c_int]),
+        "ad_conv_multi_get_long_blocks": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "ad_conv_multi_process_device": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, vp]),
         "ad_conv_multi_process_device_segment": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, i64, i64, vp]),
         "ad_conv_multi_process_device_mix": (C.c_int, [vp, vp, i64, i64, vp, i64, i64, C.c_int, i64, i64, vp]),
@@ -392,8 +397,17 @@ def _declare(L: C.CDLL) -> None:
             f"ad_{kind}_reset": (C.c_int, [vp]),
             f"ad_{kind}_destroy": (None, [vp]),
         })
+    # an older build selected through ALGODSP_LIB (A/B runs against a parent
+    # commit's library) may lack the entry points named in _NEWEST: those stay
+    # unbound and raise AttributeError when called.  Any other missing symbol
+    # is a stale build and fails here.
+    older = "ALGODSP_LIB" in os.environ
     for name, (res, args) in sig.items():
-        fn = getattr(L, name)
+        fn = getattr(L, name, None)
+        if fn is None and older and name in _NEWEST:
+            continue
+        if fn is None:
+            raise AttributeError(f"{L._name}: undefined symbol: {name}")
         fn.restype = res
         fn.argtypes = args
 

@@ -368,6 +368,8 @@ class MultiChannelConvolver(_Handle):
         self.channels = channels
         self.kernel_len = K
 
+    # the engine's three profile slots; a call that takes the long-block plan
+    # records its column / row / column kernels (A, B, C) in them
     KERNELS = ("k_window_rfft", "k_fdl_mac", "k_irfft_store")
     SCHED_SERIAL = 0     # include/algodsp.h AD_CONV_SCHED_*
     SCHED_PIPELINED = 1
@@ -384,6 +386,26 @@ class MultiChannelConvolver(_Handle):
         c = C.c_int64()
         check(lib().ad_conv_multi_get_schedule(self._h, C.byref(m), C.byref(c)))
         return m.value, c.value
+
+    LONG_AUTO = 0        # include/algodsp.h AD_CONV_LONG_*
+    LONG_OFF = 1
+    LONG_ON = 2
+    LONG_N = 1 << 21     # points per block of the long plan
+    LONG_MIN_BLOCKS = 4  # AUTO: out_len >= LONG_MIN_BLOCKS * long_hop()
+
+    def set_long_blocks(self, mode: int) -> None:
+        """Long-block plan of process_device (ad_conv_multi_set_long_blocks):
+        LONG_AUTO (long signals), LONG_OFF or LONG_ON (any whole-signal call)."""
+        check(lib().ad_conv_multi_set_long_blocks(self._h, int(mode)))
+
+    def long_blocks(self) -> int:
+        m = C.c_int()
+        check(lib().ad_conv_multi_get_long_blocks(self._h, C.byref(m)))
+        return m.value
+
+    def long_hop(self) -> int:
+        """Output samples per block of the long plan."""
+        return self.LONG_N - self.kernel_len + 1
 
     def profile_enable(self, on: bool = True, kernels: int = 7) -> None:
         """Event timing of the engine's launches; kernels: bit k = KERNELS[k]."""

@@ -1078,7 +1078,34 @@ int ad_conv_multi_get_schedule(const ad_conv* h, int* mode, int64_t* chunk_block
   });
 }
 
+int ad_conv_multi_set_long_blocks(ad_conv* h, int mode) {
+  return guard([&] {
+    if (!h || h->kind != Kind::Multi) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "not a multi-channel convolver");
+    const int m = mode == AD_CONV_LONG_AUTO ? Upols::kLongAuto
+                  : mode == AD_CONV_LONG_OFF ? Upols::kLongOff
+                  : mode == AD_CONV_LONG_ON  ? Upols::kLongOn
+                                             : -1;
+    if (m < 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "long blocks: unknown mode");
+    h->eng->set_long_blocks(m);
+  });
+}
+
+int ad_conv_multi_get_long_blocks(const ad_conv* h, int* mode) {
+  return guard([&] {
+    if (!h || h->kind != Kind::Multi) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "not a multi-channel convolver");
+    const int m = h->eng->long_blocks();
+    if (mode) *mode = m == Upols::kLongOff ? AD_CONV_LONG_OFF : m == Upols::kLongOn ? AD_CONV_LONG_ON : AD_CONV_LONG_AUTO;
+  });
+}
+
 namespace {
+// The whole-signal device call may take the long-block plan (Upols::set_long_blocks).
+struct WholeCall {
+  Upols* e;
+  explicit WholeCall(Upols* eng) : e(eng) { e->set_whole_call(true); }
+  ~WholeCall() { e->set_whole_call(false); }
+};
+
 // The row contract of the multi-channel device calls (include/algodsp.h,
 // "Device buffers"): non-null pointers, and with more than one channel a row
 // stride that holds the row.  Checked before any device work.
@@ -1103,6 +1130,7 @@ int ad_conv_multi_process_device(ad_conv* h, const double* d_in, int64_t in_stri
     h->order.enter(s);
     h->eng->begin_offline(s);
     PipeCall pc(h->eng.get());
+    WholeCall wc(h->eng.get());
     h->eng->run(d_in, in_stride, in_len, d_out, out_stride, out_len, /*use_hist=*/false, s);
     h->order.leave(s);
     h->seg_next = -1;

@@ -1,0 +1,227 @@
+// Kernels of the long-block overlap-save plan; the index map is in
+// conv_long_kernels.hpp.  A and C transform a tile of kLongW adjacent columns:
+// two real columns ride in one complex N1-point FFT (z = a + i b), so a tile
+// is kLongW / 2 transforms of FftPlan<N1>, and the tile is moved between its
+// global layout (rows of kLongW values) and the per-transform LDS images, so
+// global rows are read and written in runs of kLongW elements while each
+// 32-lane group owns whole columns.  B keeps one row in the registers of one
+// workgroup from its load to its store.
+#include "conv_long_kernels.hpp"
+
+#include "conv_kernels.hpp"
+#include "fft_device.hpp"
+
+namespace adsp {
+
+template <int M, int V>
+constexpr int last_pass_ns() {
+  return FftPlan<M, V>::ns(FftPlan<M, V>::NPASS - 1);
+}
+constexpr int N1 = kLongN1, N2 = kLongN2, W = kLongW;
+constexpr int kColThreads = 256;
+constexpr int kRowsPerInstr = kColThreads / W;  // tile rows one load / store instruction covers
+constexpr int FS = N1 + 1;                      // LDS elements per column transform (odd: spreads the images over the banks)
+using ColPlan = FftPlan<N1, 16>;
+constexpr int RV = 8;  // values per thread of the row transform
+using RowPlan = FftPlan<N2, RV>;
+static_assert(ColPlan::T * (W / 2) == kColThreads, "a tile's transforms fill the workgroup");
+static_assert(N1 % kRowsPerInstr == 0, "whole load rounds");
+
+__global__ __launch_bounds__(kColThreads) void k_long_cols_fwd(LongColArgs a) {
+  __shared__ double2 lds[(W / 2) * FS];
+  __shared__ double2 ltab[TwSplit<N1>::N];
+  const int tid = threadIdx.x;
+  const int item = xcd_remap(blockIdx.x, gridDim.x);
+  constexpr int kTiles = N2 / W;
+  const int tile = item % kTiles, cb = item / kTiles;
+  const int c = cb / a.blocks, j = cb % a.blocks;
+  const int col = tid % W, r0 = tid / W;
+  const int64_t b0 = a.start + (int64_t)j * a.hop + tile * W + col;
+  const double* x = a.x + (int64_t)c * a.x_stride;
+  double in[N1 / kRowsPerInstr];
+#pragma unroll
+  for (int i = 0; i < N1 / kRowsPerInstr; ++i) {
+    const int64_t idx = b0 + (int64_t)(r0 + kRowsPerInstr * i) * N2;
+    in[i] = (idx >= 0 && idx < a.n) ? x[idx] : 0.0;
+  }
+  const TwLds<N1> tw = tw_lds_compute<N1>(ltab, tid, kColThreads);
+  double* img = reinterpret_cast<double*>(lds + (col >> 1) * FS) + (col & 1);
+#pragma unroll
+  for (int i = 0; i < N1 / kRowsPerInstr; ++i) img[2 * lds_slot(r0 + kRowsPerInstr * i)] = in[i];
+  __syncthreads();
+  const int f = tid / ColPlan::T, t = tid % ColPlan::T;
+  double2* my = lds + f * FS;
+  double2 v[16];
+#pragma unroll
+  for (int s = 0; s < 16; ++s) v[s] = my[pass0_slot<N1, 16>(t, s)];
+  __syncthreads();
+  fft_run<N1, 16, true>(v, t, my, tw);
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 16; ++s) my[last_pass_slot<N1, 16>(t, s)] = v[s];
+  __syncthreads();
+  // separation of the two real columns: even col a = (Z[k] + conj Z[-k]) / 2,
+  // odd col b = (Z[k] - conj Z[-k]) / 2i
+  const double2* zc = lds + (col >> 1) * FS;
+  double2* T = a.T + (int64_t)cb * kLongRows * kLongPitch + tile * W + col;
+#pragma unroll
+  for (int i = 0; i <= N1 / 2 / kRowsPerInstr; ++i) {
+    const int k1 = r0 + kRowsPerInstr * i;
+    if (k1 <= N1 / 2) {
+      const double2 zk = zc[lds_slot(k1)];
+      const double2 zm = zc[lds_slot((N1 - k1) & (N1 - 1))];
+      const double2 o = (col & 1) ? make_double2(0.5 * (zk.y + zm.y), 0.5 * (zm.x - zk.x))
+                                  : make_double2(0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y));
+      st2<true>(T + (int64_t)k1 * kLongPitch, o);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kColThreads) void k_long_cols_inv(LongColArgs a) {
+  __shared__ double2 lds[(W / 2) * FS];
+  __shared__ double2 ltab[TwSplit<N1>::N];
+  const int tid = threadIdx.x;
+  const int item = xcd_remap(blockIdx.x, gridDim.x);
+  constexpr int kTiles = N2 / W;
+  const int tile = item % kTiles, cb = item / kTiles;
+  const int c = cb / a.blocks, j = cb % a.blocks;
+  const int col = tid % W, r0 = tid / W;
+  const double2* T = a.T + (int64_t)cb * kLongRows * kLongPitch + tile * W + col;
+  constexpr int NI = N1 / 2 / kRowsPerInstr + 1;
+  double2 in[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int k1 = r0 + kRowsPerInstr * i;
+    in[i] = k1 <= N1 / 2 ? ld2<true>(T + (int64_t)k1 * kLongPitch) : make_double2(0, 0);
+  }
+  const TwLds<N1> tw = tw_lds_compute<N1>(ltab, tid, kColThreads);
+  // Z = Va + i Vb over all N1 rows, rows above N1/2 from the mirror
+  // (V[N1 - k] = conj V[k]: the columns are real).  The even lane of a column
+  // pair writes row k, the odd lane row N1 - k.
+  double2* zc = lds + (col >> 1) * FS;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int k1 = r0 + kRowsPerInstr * i;
+    const double px = __shfl_xor(in[i].x, 1);
+    const double py = __shfl_xor(in[i].y, 1);
+    if (k1 <= N1 / 2) {
+      if (!(col & 1)) {  // Va = in, Vb = partner
+        const bool edge = k1 == 0 || k1 == N1 / 2;
+        zc[lds_slot(k1)] = edge ? make_double2(in[i].x, px) : make_double2(in[i].x - py, in[i].y + px);
+      } else if (k1 != 0 && k1 != N1 / 2) {  // Va = partner, Vb = in
+        zc[lds_slot(N1 - k1)] = make_double2(px + in[i].y, in[i].x - py);
+      }
+    }
+  }
+  __syncthreads();
+  const int f = tid / ColPlan::T, t = tid % ColPlan::T;
+  double2* my = lds + f * FS;
+  double2 v[16];
+#pragma unroll
+  for (int s = 0; s < 16; ++s) v[s] = my[pass0_slot<N1, 16>(t, s)];
+  __syncthreads();
+  fft_run<N1, 16, false>(v, t, my, tw);
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 16; ++s) my[last_pass_slot<N1, 16>(t, s)] = v[s];
+  __syncthreads();
+  // 8-byte stores, runs of W per row.  The per-row 16-byte pair scheme K3 uses
+  // for rows off alignment was measured here and is slower (DESIGN.md §2:
+  // C 154 us against 124 us, the step 0.418 against 0.385 ms).
+  const double* img = reinterpret_cast<const double*>(zc) + (col & 1);
+  double* y = a.y + (int64_t)c * a.y_stride;
+  const int64_t o0 = (int64_t)j * a.hop - a.skip + tile * W + col;  // output index of the column's row 0
+  const int64_t lo = (int64_t)j * a.hop;
+  const int64_t hi = a.out_len < lo + a.hop ? a.out_len : lo + a.hop;
+#pragma unroll
+  for (int i = 0; i < N1 / kRowsPerInstr; ++i) {
+    const int r = r0 + kRowsPerInstr * i;
+    const int64_t o = o0 + (int64_t)r * N2;
+    if (o >= lo && o < hi) y[o] = img[2 * lds_slot(r)];
+  }
+}
+
+// One row per workgroup of N2 / RV threads, RV values per thread.  The row's
+// pass-0 input order and its last pass's output order are both tid + T s, so
+// the forward transform's result feeds the inverse without a reshuffle.
+// BUILD: forward half only, the scaled spectrum stored to Hout (the IR's H rows).
+constexpr int kRowThreads = RowPlan::T;
+static_assert(last_pass_ns<N2, RV>() == kRowThreads, "k_long_rows relies on pass-0 order == last-pass order");
+
+// two workgroups per CU: 2 N2 / RV / 64 waves over the CU's 4 SIMDs
+constexpr int kRowWavesPerSimd = 2 * kRowThreads / 256;
+template <bool BUILD>
+__global__ __launch_bounds__(kRowThreads, kRowWavesPerSimd) void k_long_rows(LongRowArgs a) {
+  __shared__ double2 lds[N2];
+  __shared__ double2 ltab[TwSplit<N2>::N];
+  __shared__ double2 rtab[RV];
+  __shared__ double2 wtab[kRowThreads];  // each thread's own W_N^(k1 tid), parked between its two uses
+  constexpr int T = kRowThreads;
+  const int tid = threadIdx.x;
+  const int item = xcd_remap(blockIdx.x, gridDim.x);
+  const int ncb = a.blocks * a.channels;
+  const int cb = item % ncb, k1 = item / ncb;  // block and channel fastest: co-resident items share H rows
+  double2* row = a.T + ((int64_t)cb * kLongRows + k1) * kLongPitch;
+  double2 v[RV];
+#pragma unroll
+  for (int s = 0; s < RV; ++s) v[s] = ld2<true>(row + tid + T * s);
+  const TwLds<N2> tw = tw_lds_compute<N2>(ltab, tid, T);
+  // W_N^(k1 n2), n2 = tid + T s: W_N^(k1 tid) * W_N^(T k1 s)
+  if (tid < RV) {
+    double sn, cs;
+    sincospi(-2.0 * (double)(T * k1 * tid) / (double)kLongN, &sn, &cs);
+    rtab[tid] = make_double2(cs, sn);
+  }
+  {
+    double2 w0;
+    sincospi(-2.0 * (double)(k1 * tid) / (double)kLongN, &w0.y, &w0.x);
+    wtab[tid] = w0;
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < RV; ++s) v[s] = c_mul(v[s], c_mul(w0, rtab[s]));
+  }
+  // the forward transform, with the H row's loads issued behind its first
+  // pass (v is free there): they land while the later passes run
+  pass_compute_store<N2, RV, 0, true>(v, tid, lds, tw);
+  double2 h[BUILD ? 1 : RV];
+  if constexpr (!BUILD) {
+    const double2* hrow = a.H + ((int64_t)a.ir_index[cb / a.blocks] * kLongRows + k1) * kLongPitch;
+#pragma unroll
+    for (int s = 0; s < RV; ++s) h[s] = hrow[tid + T * s];
+  }
+  run_middle_passes<N2, RV, true, 1>(v, tid, lds, tw);
+  last_pass_compute<N2, RV, true>(v, tid, tw);  // v[s] = X[k1 + N1 (tid + T s)]
+  if constexpr (BUILD) {
+    double2* out = a.Hout + ((int64_t)cb * kLongRows + k1) * kLongPitch;
+#pragma unroll
+    for (int s = 0; s < RV; ++s) out[tid + T * s] = c_scale(v[s], a.scale);
+  } else {
+#pragma unroll
+    for (int s = 0; s < RV; ++s) v[s] = c_mul(v[s], h[s]);
+    __syncthreads();
+    fft_run<N2, RV, false>(v, tid, lds, tw);
+    const double2 w0 = wtab[tid];
+#pragma unroll
+    for (int s = 0; s < RV; ++s) st2<true>(row + tid + T * s, c_mul(v[s], c_conj(c_mul(w0, rtab[s]))));
+  }
+}
+
+void launch_long_cols_fwd(const LongColArgs& a, hipStream_t s) {
+  const unsigned items = (unsigned)a.channels * a.blocks * (N2 / W);
+  timed_launch(k_long_cols_fwd, dim3(items), dim3(kColThreads), s, a);
+}
+
+void launch_long_rows(const LongRowArgs& a, bool build_h, hipStream_t s) {
+  const unsigned items = (unsigned)a.channels * a.blocks * kLongRows;
+  if (build_h)
+    timed_launch(k_long_rows<true>, dim3(items), dim3(kRowThreads), s, a);
+  else
+    timed_launch(k_long_rows<false>, dim3(items), dim3(kRowThreads), s, a);
+}
+
+void launch_long_cols_inv(const LongColArgs& a, hipStream_t s) {
+  const unsigned items = (unsigned)a.channels * a.blocks * (N2 / W);
+  timed_launch(k_long_cols_inv, dim3(items), dim3(kColThreads), s, a);
+}
+
+}  // namespace adsp

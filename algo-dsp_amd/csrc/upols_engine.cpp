@@ -90,6 +90,7 @@ Upols::Upols(int device, const double* kernels, int n_ir, int64_t K, int L, int 
     if (irm[c] < 0 || irm[c] >= n_ir_) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "ir_index out of range");
   irmap_.alloc(C_);
   AD_HIP(hipMemcpyAsync(irmap_.p, irm.data(), C_ * sizeof(int), hipMemcpyHostToDevice, stream_));
+  if (K_ <= kLongN / 4) taps_.assign(kernels, kernels + (size_t)n_ir_ * K_);
   if (K_ == 1) {  // kernels is [n_ir][1]
     tap0_.alloc((size_t)n_ir_);
     AD_HIP(hipMemcpyAsync(tap0_.p, kernels, (size_t)n_ir_ * sizeof(double), hipMemcpyHostToDevice, stream_));
@@ -383,6 +384,11 @@ void Upols::run(const double* d_in, int64_t in_stride, int64_t n, double* d_out,
   // call blocks holding input samples: [0, nb_in); K1 transforms only those,
   // K2 reads every later block as zeros
   const int64_t nb_in = (std::max<int64_t>(n, 0) + L_ - 1) / L_;
+  if (takes_long(io, use_hist, jb, je)) {
+    run_long(io, s);
+    g_next_ += J;
+    return;
+  }
   if (sig_pipe_ && pipe_call_ && !use_hist && !accumulate && !gate_on_) {
     run_pipelined(io, s, jb, J, nb_in);
     return;
@@ -420,6 +426,104 @@ void Upols::run(const double* d_in, int64_t in_stride, int64_t n, double* d_out,
     AD_HIP(hipGetLastError());
     g_next_ += ck.jc;
   }
+}
+
+void Upols::set_long_blocks(int mode) {
+  if (mode != kLongAuto && mode != kLongOff && mode != kLongOn) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "unknown long-block mode");
+  long_mode_ = mode;
+}
+
+bool Upols::takes_long(const Io& io, bool use_hist, int64_t jb, int64_t je) const {
+  if (long_mode_ == kLongOff || !whole_call_ || taps_.empty() || single_tap_) return false;
+  if (sched_mode_ != kSchedSerial || use_hist || io.accumulate || io.mix || gate_on_) return false;
+  if (jb != 0 || je * L_ < io.out_len) return false;
+  return long_mode_ == kLongOn || io.out_len >= kLongMinBlocks * long_hop();
+}
+
+// H and the intermediates of the long plan.  H: once per handle.  T: grown to
+// the largest call so far; both are freed with the engine.
+void Upols::ensure_long(int64_t blocks, hipStream_t s) {
+  const size_t per_block = (size_t)kLongRows * kLongPitch;
+  if (blocks > tl_blocks_ || !TL_.p) {
+    // a resized buffer: no kernel of an earlier call may still use the old one
+    if (TL_.p) AD_HIP(hipStreamSynchronize(s));
+    // alloc frees the old buffer first: a failed regrow must leave "nothing
+    // held", so that the next call allocates again instead of launching on null
+    tl_blocks_ = 0;
+    TL_.alloc((size_t)C_ * blocks * per_block);
+    tl_blocks_ = blocks;
+  }
+  if (HL_.p) return;
+  // H is built into a local buffer and handed to the engine only once every
+  // step has succeeded: an error on the way leaves HL_ empty, and the next
+  // long call builds it again
+  DevBuf<double> dtaps;
+  DevBuf<double2> tmp, hnew;
+  dtaps.alloc(taps_.size());
+  tmp.alloc((size_t)n_ir_ * per_block);
+  hnew.alloc((size_t)n_ir_ * per_block);
+  AD_HIP(hipMemcpyAsync(dtaps.p, taps_.data(), taps_.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  LongColArgs a{};
+  a.x = dtaps.p;
+  a.x_stride = K_;
+  a.n = K_;
+  a.start = 0;
+  a.hop = 0;
+  a.blocks = 1;
+  a.channels = n_ir_;
+  a.T = tmp.p;
+  launch_long_cols_fwd(a, s);
+  LongRowArgs b{};
+  b.T = tmp.p;
+  b.blocks = 1;
+  b.channels = n_ir_;
+  b.Hout = hnew.p;
+  b.scale = 1.0 / (double)kLongN;  // the inverse transforms are unnormalised
+  launch_long_rows(b, /*build_h=*/true, s);
+  AD_HIP(hipGetLastError());
+  AD_HIP(hipStreamSynchronize(s));  // dtaps and tmp must outlive the launches
+  std::swap(HL_.p, hnew.p);
+  std::swap(HL_.n, hnew.n);
+}
+
+void Upols::run_long(const Io& io, hipStream_t s) {
+  const int64_t hop = long_hop();
+  const int blocks = (int)((io.out_len + hop - 1) / hop);
+  ensure_long(blocks, s);  // ahead of prof_begin: H's kernels are not the step's
+  const double cb = (double)C_ * blocks, tbytes = (double)kLongRows * kLongN2 * 16;
+  LongColArgs a{};
+  a.x = io.in;
+  a.x_stride = io.in_stride;
+  a.n = io.n;
+  a.start = -(K_ - 1);
+  a.hop = hop;
+  a.blocks = blocks;
+  a.channels = C_;
+  a.T = TL_.p;
+  a.y = io.out;
+  a.y_stride = io.out_stride;
+  a.out_len = io.out_len;
+  a.skip = K_ - 1;
+  hipEvent_t e0;
+  // algorithmic bytes: the signal once plus each block's K-1 overlap in, the
+  // kept rows out; rows in and out plus H once; rows in, the outputs out
+  prof_begin(s, &e0, 0);
+  launch_long_cols_fwd(a, s);
+  prof_end(s, e0, 0, (double)C_ * std::min<double>((double)std::max<int64_t>(io.n, 0), (double)blocks * hop) * 8 +
+                         cb * (double)(K_ - 1) * 8 + cb * tbytes);
+  LongRowArgs b{};
+  b.T = TL_.p;
+  b.blocks = blocks;
+  b.channels = C_;
+  b.H = HL_.p;
+  b.ir_index = irmap_.p;
+  prof_begin(s, &e0, 1);
+  launch_long_rows(b, /*build_h=*/false, s);
+  prof_end(s, e0, 1, 2 * cb * tbytes + (double)n_ir_ * tbytes);
+  prof_begin(s, &e0, 2);
+  launch_long_cols_inv(a, s);
+  prof_end(s, e0, 2, cb * tbytes + (double)C_ * io.out_len * 8);
+  AD_HIP(hipGetLastError());
 }
 
 // The pipelined offline schedule (set_schedule): chunk k's K1 on the caller's

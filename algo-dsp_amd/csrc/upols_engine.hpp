@@ -12,6 +12,7 @@
 
 #include "ad_common.hpp"
 #include "conv_kernels.hpp"
+#include "conv_long_kernels.hpp"
 
 namespace adsp {
 
@@ -96,6 +97,20 @@ class Upols {
   // the device entry points opt in (the host-buffer pipeline and the
   // partitioned stages call run() with their own streams and stay serial)
   void set_pipeline_call(bool on) { pipe_call_ = on; }
+  // Long-block plan (conv_long_kernels.hpp): a whole-signal device call with
+  // no history, accumulate, gate or mix under the serial schedule runs as
+  // A -> B -> C over blocks of kLongN points (hop kLongN - K + 1) when
+  // K <= kLongN / 4 and, under AUTO, the output spans at least kLongMinBlocks
+  // of those hops.  ON forces it for every such call, OFF never takes it.  Its
+  // results differ from the UPOLS plan's in the last bits; the delay line is
+  // left untouched (the next offline signal restarts it anyway).
+  static constexpr int kLongAuto = 0, kLongOff = 1, kLongOn = 2;
+  static constexpr int kLongMinBlocks = 4;
+  void set_long_blocks(int mode);
+  int long_blocks() const { return long_mode_; }
+  int64_t long_hop() const { return kLongN - K_ + 1; }
+  // the whole-signal device entry point opts in, as set_pipeline_call does
+  void set_whole_call(bool on) { whole_call_ = on; }
   // Kept for API symmetry: the ring already holds the last block's spectrum
   // (checks that a streaming call covers at least one hop).
   void save_history(const double* d_in, int64_t in_stride, int64_t n, hipStream_t s);
@@ -162,6 +177,16 @@ class Upols {
   hipStream_t ps_[2] = {nullptr, nullptr};  // K2, K3 streams
   hipEvent_t pev_[3][4] = {};               // K1 / K2 / K3 done, per chunk mod 4
   void ensure_pipe();
+
+  int long_mode_ = kLongAuto;
+  bool whole_call_ = false;
+  std::vector<double> taps_;  // host [n_ir][K], kept for the long plan's H
+  DevBuf<double2> HL_;        // [n_ir][kLongRows][kLongPitch], built at the first long call
+  DevBuf<double2> TL_;        // [C * blocks][kLongRows][kLongPitch]
+  int64_t tl_blocks_ = 0;     // blocks per channel TL_ holds
+  bool takes_long(const Io& io, bool use_hist, int64_t jb, int64_t je) const;
+  void ensure_long(int64_t blocks, hipStream_t s);
+  void run_long(const Io& io, hipStream_t s);
 
   struct ProfRec {
     hipEvent_t start, stop;

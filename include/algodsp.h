@@ -224,6 +224,23 @@ int ad_conv_multi_create(const double* kernels, int n_ir, int64_t kernel_len, in
 #define AD_CONV_SCHED_CHUNKED 2 /* PIPELINED's chunks and rings, every kernel on the caller's stream */
 int ad_conv_multi_set_schedule(ad_conv* h, int mode, int64_t chunk_blocks, int64_t run_blocks);
 int ad_conv_multi_get_schedule(const ad_conv* h, int* mode, int64_t* chunk_blocks);
+/* Long-block plan of ad_conv_multi_process_device: under the SERIAL schedule a
+ * whole-signal call with kernel_len <= 2^19 may run as overlap-save over
+ * blocks of one 2^21-point real FFT (hop 2^21 - kernel_len + 1) instead of
+ * the partitioned engine, which moves about two thirds of the bytes.  AUTO
+ * (the default) takes it when out_len spans at least 4 such hops, ON for any
+ * such call, OFF never.  The entry points are bit-identical to each other
+ * within a plan; a call that takes the long plan differs from the segment,
+ * mix and host forms of the same signal in the last bits (both are within the
+ * 1e-9 bound), and OFF restores the equality.  The first long call of a handle
+ * builds the IR's long spectra and allocates the intermediates (16.9 MB per
+ * IR plus 16.9 MB per channel and block), freed with the handle.
+ * get_schedule and ad_conv_fft_size do not change.                          */
+#define AD_CONV_LONG_AUTO 0
+#define AD_CONV_LONG_OFF 1
+#define AD_CONV_LONG_ON 2
+int ad_conv_multi_set_long_blocks(ad_conv* h, int mode);
+int ad_conv_multi_get_long_blocks(const ad_conv* h, int* mode);
 /* Full linear convolution of every channel (ModeFull semantics per channel):
  * d_in  [channels][in_stride] (first in_len used),
  * d_out [channels][out_stride] (first out_len written; out_len <= in_len+K-1).
