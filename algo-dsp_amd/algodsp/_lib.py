@@ -158,6 +158,21 @@ class BitCrusherConfig(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("sample_rate", "bit_depth", "mix")] + [("downsample", C.c_int)]
 
 
+class TransientConfig(C.Structure):
+    """ad_transient_config (include/algodsp.h); field k is parameter AD_TRANSIENT_* = k."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "attack_amount", "sustain_amount", "attack_ms", "release_ms",
+                                          "attack_coeff", "release_coeff")]
+
+
+class DeEsserConfig(C.Structure):
+    """ad_deesser_config (include/algodsp.h); field k is parameter AD_DEESSER_* = k."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "freq_hz", "q", "threshold_db", "ratio", "knee_db",
+                                          "attack_ms", "release_ms", "range_db", "attack_coeff", "release_coeff")] + \
+               [(n, C.c_int) for n in ("mode", "detector", "listen", "filter_order")]
+
+
 class FxNodeCfg(C.Structure):
     """ad_fx_node_cfg: a node's own config structure and its size."""
 
@@ -365,6 +380,17 @@ def _declare(L: C.CDLL) -> None:
         "ad_distortion_curve": (C.c_int, [vp, c_double_p, i64, c_double_p]),
         "ad_bitcrusher_derived": (C.c_int, [vp, C.c_int, c_double_p, C.POINTER(C.c_int), c_double_p]),
         "ad_bitcrusher_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
+        "ad_transient_derived": (C.c_int, [C.POINTER(TransientConfig), c_double_p, c_double_p]),
+        "ad_transient_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
+        "ad_transient_get_state": (C.c_int, [vp, C.c_int, c_double_p]),
+        "ad_transient_set_state": (C.c_int, [vp, C.c_int, C.c_double]),
+        "ad_deesser_derived": (C.c_int, [C.POINTER(DeEsserConfig)] + [c_double_p] * 7),
+        "ad_deesser_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 4),
+        "ad_deesser_get_state": (C.c_int, [vp, C.c_int, c_double_p, c_double_p, c_double_p]),
+        "ad_deesser_set_state": (C.c_int, [vp, C.c_int, C.c_double, c_double_p, c_double_p]),
+        "ad_deesser_metrics": (C.c_int, [vp, C.c_int, c_double_p, c_double_p]),
+        "ad_deesser_reset_metrics": (C.c_int, [vp]),
+        "ad_deesser_gain": (C.c_int, [vp, c_double_p, c_double_p, i64]),
         "ad_correlate_fft": (C.c_int, [c_double_p, i64, c_double_p, i64, c_double_p, C.c_int]),
         "ad_correlate_fft_device": (C.c_int, [vp, i64, vp, i64, vp, C.c_int, vp]),
         "ad_deconv_default_options": (DeconvOptionsC, []),
@@ -385,8 +411,9 @@ def _declare(L: C.CDLL) -> None:
             f"ad_{kind}_reset": (C.c_int, [vp]),
             f"ad_{kind}_destroy": (None, [vp]),
         })
-    for kind, cfg in (("distortion", DistortionConfig), ("bitcrusher", BitCrusherConfig)):
-        sig.update({  # the two waveshaping handles share these prototypes
+    for kind, cfg in (("distortion", DistortionConfig), ("bitcrusher", BitCrusherConfig),
+                      ("transient", TransientConfig), ("deesser", DeEsserConfig)):
+        sig.update({  # the waveshaping and the newer dynamics handles share these prototypes
             f"ad_{kind}_default_config": (None, [C.POINTER(cfg), C.c_double]),
             f"ad_{kind}_validate": (C.c_int, [C.POINTER(cfg)]),
             f"ad_{kind}_create": (C.c_int, [C.POINTER(cfg), C.c_int, C.c_int, C.POINTER(vp)]),

@@ -13,15 +13,16 @@ its runtime's Configure does (runtime_dynamics.go, runtime_filter_pitch_reverb.g
 chain_process.go:177-227 for split-freq).  The compiled node list goes to
 ad_fx_graph_create (include/algodsp.h), which runs every node on the GPU;
 there is no CPU path.  Node types outside {filter*, dyn-compressor,
-dyn-limiter, dyn-gate, dyn-expander, reverb-freeverb, reverb-fdn, reverb,
-reverb-conv, delay, delay-simple, flanger, phaser, tremolo, ringmod, distortion,
-dist-cheb, bitcrusher, split-freq, split, sum, _input, _output} raise
+dyn-limiter, dyn-gate, dyn-expander, dyn-deesser, dyn-transient,
+reverb-freeverb, reverb-fdn, reverb, reverb-conv, delay, delay-simple, flanger,
+phaser, tremolo, ringmod, distortion, dist-cheb, bitcrusher, split-freq, split,
+sum, _input, _output} raise
 UnknownEffect (the GPU runtime's ErrUnknownEffect).  The phaser, tremolo and
 ringmod nodes carry their configuration in a parallel array (_NodeExt,
 ad_fx_graph_create_ext); _Node keeps its layout.  The distortion, dist-cheb
 and bitcrusher nodes carry theirs as (structure, size) in a second parallel
-array (FxNodeCfg, ad_fx_graph_create_cfg), which later node types can use as
-it is.
+array (FxNodeCfg, ad_fx_graph_create_cfg), and so do dyn-deesser and
+dyn-transient.
 """
 from __future__ import annotations
 
@@ -32,8 +33,9 @@ import math
 import numpy as np
 
 from . import design
-from ._lib import (BitCrusherConfig, CompressorConfig, DelayConfig, DistortionConfig, FdnConfig, FlangerConfig,
-                   FxNodeCfg, PhaserConfig, RingModConfig, TremoloConfig, check, lib, ptr)
+from ._lib import (BitCrusherConfig, CompressorConfig, DeEsserConfig, DelayConfig, DistortionConfig, FdnConfig,
+                   FlangerConfig, FxNodeCfg, PhaserConfig, RingModConfig, TransientConfig, TremoloConfig, check, lib,
+                   ptr)
 from .processors import section_table
 
 INPUT_NODE_ID = "_input"  # graph.go:10-13
@@ -45,6 +47,7 @@ FXN_FDN_REVERB = 8
 FXN_DELAY, FXN_FLANGER = 9, 10
 FXN_PHASER, FXN_TREMOLO, FXN_RINGMOD = 11, 12, 13
 FXN_DISTORTION, FXN_BITCRUSHER = 15, 16  # 14 is not assigned
+FXN_DEESSER, FXN_TRANSIENT = 18, 19  # 17 is not assigned
 MAX_PARENTS = 8
 
 FILTER_TYPES = ("filter", "filter-lowpass", "filter-highpass", "filter-bandpass", "filter-notch",
@@ -392,6 +395,39 @@ def bitcrusher_params(p: Params, fs: float) -> BitCrusherConfig:
     return c
 
 
+def deesser_params(p: Params, fs: float) -> DeEsserConfig:
+    """deesserRuntime.Configure (runtime_dynamics.go:244-310): the clamped
+    values it hands to the setters of a NewDeEsser(fs), in its order; the mode
+    and detector strings as normalize.go:207-227 reads them (anything unknown
+    is split band / bandpass).  Coefficients 0: the library derives them."""
+    c = DeEsserConfig()
+    c.sample_rate = float(fs)
+    c.freq_hz = clamp(p.GetNum("freqHz", 6000), 1000, fs * 0.49)
+    c.q = clamp(p.GetNum("q", 1.5), 0.1, 10)
+    c.threshold_db = clamp(p.GetNum("thresholdDB", -20), -80, 0)
+    c.ratio = clamp(p.GetNum("ratio", 4), 1, 100)
+    c.knee_db = clamp(p.GetNum("kneeDB", 3), 0, 12)
+    c.attack_ms = clamp(p.GetNum("attackMs", 0.5), 0.01, 50)
+    c.release_ms = clamp(p.GetNum("releaseMs", 20), 1, 500)
+    c.range_db = clamp(p.GetNum("rangeDB", -24), -60, 0)
+    c.mode = 1 if p.Str.get("mode") == "wideband" else 0
+    c.detector = 1 if p.Str.get("detector") == "highpass" else 0
+    c.filter_order = min(max(int(_go_round(p.GetNum("filterOrder", 2))), 1), 4)
+    c.listen = 1 if p.GetNum("listen", 0) >= 0.5 else 0
+    return c
+
+
+def transient_params(p: Params, fs: float) -> TransientConfig:
+    """transientShaperRuntime.Configure (runtime_dynamics.go:320-347).  Coefficients 0: the library derives them."""
+    c = TransientConfig()
+    c.sample_rate = float(fs)
+    c.attack_amount = clamp(p.GetNum("attack", 0), -1, 1)
+    c.sustain_amount = clamp(p.GetNum("sustain", 0), -1, 1)
+    c.attack_ms = clamp(p.GetNum("attackMs", 10), 0.1, 200)
+    c.release_ms = clamp(p.GetNum("releaseMs", 120), 1, 2000)
+    return c
+
+
 def _config_dict(cfg) -> dict:
     """A config structure's fields as plain data (arrays as lists)."""
     return {f: (list(getattr(cfg, f)) if isinstance(getattr(cfg, f), C.Array) else getattr(cfg, f))
@@ -639,6 +675,25 @@ class Chain:
                 keep.append(cfg)
                 cfgs[i].config, cfgs[i].bytes = C.addressof(cfg), C.sizeof(cfg)
                 sd.update(type="bitcrusher", bitcrusher=_config_dict(cfg))
+            elif t == "dyn-deesser":
+                d.type = FXN_DEESSER
+                # the factory builds NewDeEsser(fs) first and Configure's SetSampleRate runs with the default
+                # 6000 Hz in place (deesser.go:399): a sample rate <= 12 kHz fails before freqHz is read
+                base = DeEsserConfig()
+                lib().ad_deesser_default_config(C.byref(base), fs)
+                check(lib().ad_deesser_validate(C.byref(base)))
+                cfg = deesser_params(p, fs)
+                check(lib().ad_deesser_validate(C.byref(cfg)))
+                keep.append(cfg)
+                cfgs[i].config, cfgs[i].bytes = C.addressof(cfg), C.sizeof(cfg)
+                sd.update(type="deesser", deesser=_config_dict(cfg))
+            elif t == "dyn-transient":
+                d.type = FXN_TRANSIENT
+                cfg = transient_params(p, fs)
+                check(lib().ad_transient_validate(C.byref(cfg)))
+                keep.append(cfg)
+                cfgs[i].config, cfgs[i].bytes = C.addressof(cfg), C.sizeof(cfg)
+                sd.update(type="transient", transient=_config_dict(cfg))
             elif t in ("reverb-freeverb", "reverb"):  # reverbRuntime without model "fdn" is Freeverb
                 d.type = FXN_FREEVERB
                 for j, v in enumerate(freeverb_params(p)):

@@ -14,6 +14,8 @@ like the reference's own tests:
   modulation.RingModulator       dsp/effects/modulation/ring_modulator.go
   effects.Distortion             dsp/effects/distortion.go
   effects.BitCrusher             dsp/effects/bit_crusher.go
+  dynamics.TransientShaper       dsp/effects/dynamics/transient_shaper.go
+  dynamics.DeEsser               dsp/effects/dynamics/deesser.go
   fir.Filter                     dsp/filter/fir/filter.go
   effectchain filter -> dyn-compressor -> reverb-freeverb (EffectChain)
 
@@ -27,8 +29,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (BitCrusherConfig, CompressorConfig, DelayConfig, DistortionConfig, FdnConfig, FlangerConfig,
-                   PhaserConfig, RingModConfig, TremoloConfig, check, f64, lib, ptr)
+from ._lib import (BitCrusherConfig, CompressorConfig, DeEsserConfig, DelayConfig, DistortionConfig, FdnConfig,
+                   FlangerConfig, PhaserConfig, RingModConfig, TransientConfig, TremoloConfig, check, f64, lib, ptr)
 
 DEVICE = 0
 SEC_STRIDE = 6  # {pre_gain, b0, b1, b2, a1, a2}
@@ -959,6 +961,242 @@ class BitCrusher(_ShaperHandle):
         v = [C.c_int() for _ in range(3)]
         check(lib().ad_bitcrusher_kernel_info(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+
+class _DynHandle(_Handle):
+    """What TransientShaper and DeEsser share: a config structure, options as
+    keywords, set_param with the int parameters as whole numbers, and the
+    host-only derived values of a config."""
+
+    _config = None
+    _options = ()
+    _int_options = ()
+
+    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        cfg = self._config()
+        if config is None:
+            self._fn("default_config")(C.byref(cfg), float(sample_rate))
+        else:
+            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        for k, v in options.items():
+            if k in self._int_options:
+                setattr(cfg, k, int(v))
+            elif k in self._options:
+                setattr(cfg, k, float(v))
+            else:
+                raise TypeError(f"unknown {self._kind} option {k!r}")
+        check(self._fn("create")(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+
+    def _set(self, which: int, v):
+        check(self._fn("set_param")(self._h, which, float(v)))
+
+    def config(self):
+        cfg = self._config()
+        check(self._fn("get_config")(self._h, C.byref(cfg)))
+        return cfg
+
+    def SetSampleRate(self, v):
+        self._set(0, v)
+
+    def SetAttack(self, v):
+        self._set(self.P_ATTACK, v)
+
+    def SetRelease(self, v):
+        self._set(self.P_RELEASE, v)
+
+    def SetAttackCoeff(self, v):  # attackCoeff, for a caller whose exp is not the C library's
+        self._set(self.P_ATTACK_COEFF, v)
+
+    def SetReleaseCoeff(self, v):
+        self._set(self.P_RELEASE_COEFF, v)
+
+    def SampleRate(self) -> float:
+        return self.config().sample_rate
+
+    def Attack(self) -> float:
+        return self.config().attack_ms
+
+    def Release(self) -> float:
+        return self.config().release_ms
+
+
+def transient_derived(cfg: TransientConfig):
+    """(attack_coeff, release_coeff) in use for a config, of ad_transient_derived: host only."""
+    a, r = C.c_double(), C.c_double()
+    check(lib().ad_transient_derived(C.byref(cfg), C.byref(a), C.byref(r)))
+    return a.value, r.value
+
+
+def deesser_derived(cfg: DeEsserConfig) -> dict:
+    """dict(section=(b0, b1, b2, a1, a2), band_norm, threshold_log2, knee_width_log2, range_lin, attack_coeff,
+    release_coeff) for a config, of ad_deesser_derived: what the reference caches, host only."""
+    sec = (C.c_double * 5)()
+    v = [C.c_double() for _ in range(6)]
+    check(lib().ad_deesser_derived(C.byref(cfg), sec, *[C.byref(x) for x in v]))
+    return dict(section=tuple(sec), band_norm=v[0].value, threshold_log2=v[1].value, knee_width_log2=v[2].value,
+                range_lin=v[3].value, attack_coeff=v[4].value, release_coeff=v[5].value)
+
+
+class TransientShaper(_DynHandle):
+    """dynamics.TransientShaper (transient_shaper.go:25-200) for `channels`
+    instances sharing one configuration: NewTransientShaper(sample_rate) with
+    options as keywords (attack_amount, sustain_amount, attack_ms, release_ms,
+    attack_coeff, release_coeff), or `config` (a TransientConfig) applied
+    whole.  A rejected setter value raises ErrInvalidArgument and changes
+    nothing."""
+
+    (P_SAMPLE_RATE, P_ATTACK_AMOUNT, P_SUSTAIN_AMOUNT, P_ATTACK, P_RELEASE, P_ATTACK_COEFF,
+     P_RELEASE_COEFF) = range(7)  # AD_TRANSIENT_*
+    _kind = "transient"
+    _config = TransientConfig
+    _options = ("attack_amount", "sustain_amount", "attack_ms", "release_ms", "attack_coeff", "release_coeff")
+
+    def SetAttackAmount(self, v):  # :57-66
+        self._set(self.P_ATTACK_AMOUNT, v)
+
+    def SetSustainAmount(self, v):  # :69-78
+        self._set(self.P_SUSTAIN_AMOUNT, v)
+
+    def AttackAmount(self) -> float:  # :120-132
+        return self.config().attack_amount
+
+    def SustainAmount(self) -> float:
+        return self.config().sustain_amount
+
+    def derived(self):
+        return transient_derived(self.config())
+
+    def kernel_info(self):
+        """(channels per workgroup, samples staged per chunk, lds_bytes) of the walk, of ad_transient_kernel_info."""
+        v = [C.c_int() for _ in range(3)]
+        check(lib().ad_transient_kernel_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def get_state(self, channel: int = 0) -> float:
+        """The envelope of `channel`."""
+        e = C.c_double()
+        check(lib().ad_transient_get_state(self._h, int(channel), C.byref(e)))
+        return e.value
+
+    def set_state(self, channel: int, envelope: float):
+        check(lib().ad_transient_set_state(self._h, int(channel), float(envelope)))
+
+
+class DeEsser(_DynHandle):
+    """dynamics.DeEsser (deesser.go:100-622) for `channels` instances sharing
+    one configuration: NewDeEsser(sample_rate) with options as keywords
+    (freq_hz, q, threshold_db, ratio, knee_db, attack_ms, release_ms, range_db,
+    attack_coeff, release_coeff, mode, detector, listen, filter_order), or
+    `config` (a DeEsserConfig) applied whole.  A rejected setter value raises
+    ErrInvalidArgument and changes nothing."""
+
+    (P_SAMPLE_RATE, P_FREQ, P_Q, P_THRESHOLD, P_RATIO, P_KNEE, P_ATTACK, P_RELEASE, P_RANGE, P_ATTACK_COEFF,
+     P_RELEASE_COEFF, P_MODE, P_DETECTOR, P_LISTEN, P_FILTER_ORDER) = range(15)  # AD_DEESSER_*
+    SPLIT_BAND, WIDEBAND = 0, 1  # DeEsserMode :15-25
+    DETECT_BANDPASS, DETECT_HIGHPASS = 0, 1  # DeEsserDetector :30-39
+    _kind = "deesser"
+    _config = DeEsserConfig
+    _options = ("freq_hz", "q", "threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "range_db",
+                "attack_coeff", "release_coeff")
+    _int_options = ("mode", "detector", "listen", "filter_order")
+
+    def SetFrequency(self, v):  # :228-244
+        self._set(self.P_FREQ, v)
+
+    def SetQ(self, v):  # :248-259
+        self._set(self.P_Q, v)
+
+    def SetThreshold(self, v):  # :263-272
+        self._set(self.P_THRESHOLD, v)
+
+    def SetRatio(self, v):  # :276-287
+        self._set(self.P_RATIO, v)
+
+    def SetKnee(self, v):  # :291-302
+        self._set(self.P_KNEE, v)
+
+    def SetRange(self, v):  # :336-347
+        self._set(self.P_RANGE, v)
+
+    def SetMode(self, v):  # :350-358
+        self._set(self.P_MODE, v)
+
+    def SetDetector(self, v):  # :361-370
+        self._set(self.P_DETECTOR, v)
+
+    def SetListen(self, on: bool):  # :375-377
+        self._set(self.P_LISTEN, 1 if on else 0)
+
+    def SetFilterOrder(self, v):  # :381-391
+        self._set(self.P_FILTER_ORDER, v)
+
+    def Frequency(self) -> float:  # :186-222
+        return self.config().freq_hz
+
+    def Q(self) -> float:
+        return self.config().q
+
+    def Threshold(self) -> float:
+        return self.config().threshold_db
+
+    def Ratio(self) -> float:
+        return self.config().ratio
+
+    def Knee(self) -> float:
+        return self.config().knee_db
+
+    def Range(self) -> float:
+        return self.config().range_db
+
+    def Mode(self) -> int:
+        return self.config().mode
+
+    def Detector(self) -> int:
+        return self.config().detector
+
+    def Listen(self) -> bool:
+        return bool(self.config().listen)
+
+    def FilterOrder(self) -> int:
+        return self.config().filter_order
+
+    def GetMetrics(self, channel: int = 0):  # :499-501 -> (DetectionLevel, GainReduction)
+        d, g = C.c_double(), C.c_double()
+        check(lib().ad_deesser_metrics(self._h, int(channel), C.byref(d), C.byref(g)))
+        return d.value, g.value
+
+    def ResetMetrics(self):  # :504-506
+        check(lib().ad_deesser_reset_metrics(self._h))
+
+    def derived(self) -> dict:
+        return deesser_derived(self.config())
+
+    def kernel_info(self):
+        """(channels per workgroup, samples staged per chunk, lds_bytes, cascades walked) of the walk the next
+        call runs, of ad_deesser_kernel_info."""
+        v = [C.c_int() for _ in range(4)]
+        check(lib().ad_deesser_kernel_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def get_state(self, channel: int = 0):
+        """(envelope, detect [4][2], band [4][2]) of `channel`: {d0, d1} of each section."""
+        e = C.c_double()
+        det, band = np.zeros((4, 2)), np.zeros((4, 2))
+        check(lib().ad_deesser_get_state(self._h, int(channel), C.byref(e), ptr(det), ptr(band)))
+        return e.value, det, band
+
+    def set_state(self, channel: int, envelope: float, detect, band):
+        det, bnd = f64(detect).reshape(4, 2), f64(band).reshape(4, 2)
+        check(lib().ad_deesser_set_state(self._h, int(channel), float(envelope), ptr(det), ptr(bnd)))
+
+    def gain(self, levels):
+        """calculateGain(level) by the device code a call runs.  Nothing advances."""
+        lv = f64(levels).reshape(-1)
+        out = np.empty_like(lv)
+        check(lib().ad_deesser_gain(self._h, ptr(lv), ptr(out), int(lv.size)))
+        return out.reshape(np.shape(levels))
 
 
 class EffectChain(_FxChain):

@@ -25,7 +25,8 @@
 //     the high band on a copy;
 //   * the reverbs other than Freeverb, the delays and the modulation effects
 //     (flanger, phaser, tremolo, ringmod) and the waveshapers (distortion,
-//     dist-cheb, bitcrusher) are ops of their own on their handles;
+//     dist-cheb, bitcrusher), the de-esser and the transient shaper are ops
+//     of their own on their handles;
 //   * independent branches run concurrently on up to 8 streams (schedule()).
 #include <hip/hip_runtime.h>
 
@@ -99,8 +100,21 @@ struct BitcrusherDel {
 };
 using BitcrusherPtr = std::unique_ptr<ad_bitcrusher, BitcrusherDel>;
 
+struct DeesserDel {
+  void operator()(ad_deesser* f) const { ad_deesser_destroy(f); }
+};
+using DeesserPtr = std::unique_ptr<ad_deesser, DeesserDel>;
+
+struct TransientDel {
+  void operator()(ad_transient* f) const { ad_transient_destroy(f); }
+};
+using TransientPtr = std::unique_ptr<ad_transient, TransientDel>;
+
 struct FxOp {
-  enum Kind { ZERO, COPY, MIX, CHAIN, CONV, FDN, DELAY, FLANGER, PHASER, TREMOLO, RINGMOD, DISTORTION, BITCRUSHER } kind;
+  enum Kind {
+    ZERO, COPY, MIX, CHAIN, CONV, FDN, DELAY, FLANGER, PHASER, TREMOLO, RINGMOD, DISTORTION, BITCRUSHER, DEESSER,
+    TRANSIENT
+  } kind;
   int dst = -1;                 // buffer id (written; CHAIN and later kinds: read and written in place)
   std::vector<int> srcs;        // COPY / MIX: buffers read
   ad_fx_chain* chain = nullptr;   // CHAIN
@@ -113,6 +127,8 @@ struct FxOp {
   ad_ringmod* ringmod = nullptr;  // RINGMOD
   ad_distortion* distortion = nullptr;  // DISTORTION
   ad_bitcrusher* bitcrusher = nullptr;  // BITCRUSHER
+  ad_deesser* deesser = nullptr;        // DEESSER
+  ad_transient* transient = nullptr;    // TRANSIENT
   // schedule (see schedule()): lane 0 is the caller's stream
   int lane = 0;
   std::vector<int> waits;  // ops on other lanes this op waits for
@@ -147,6 +163,8 @@ struct ad_fx_graph {
   std::vector<RingmodPtr> ringmods;
   std::vector<DistortionPtr> distortions;
   std::vector<BitcrusherPtr> bitcrushers;
+  std::vector<DeesserPtr> deessers;
+  std::vector<TransientPtr> transients;
   DevBuf<double> pool;   // buffers 1..nbuf-1, [nbuf-1][channels][cap]
   int64_t cap = 0;
   DevBuf<double> work;   // host-call staging
@@ -174,6 +192,8 @@ struct ad_fx_graph {
     ringmods.clear();
     distortions.clear();
     bitcrushers.clear();
+    deessers.clear();
+    transients.clear();
     if (stream) {
       (void)hipStreamSynchronize(stream);
       (void)lib_stream_destroy(stream);
@@ -225,7 +245,8 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
   int out_node = -1;
   for (int i = 0; i < n; ++i) {
     const ad_fx_node& d = nodes[i];
-    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_BITCRUSHER || (d.type > AD_FXN_RINGMOD && d.type < AD_FXN_DISTORTION))
+    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_TRANSIENT || (d.type > AD_FXN_RINGMOD && d.type < AD_FXN_DISTORTION) ||
+        (d.type > AD_FXN_BITCRUSHER && d.type < AD_FXN_DEESSER))
       AD_FAIL(AD_ERR_UNKNOWN_EFFECT, "fx graph: node type not supported by the GPU runtime");
     if (d.type == AD_FXN_INPUT && i != 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: more than one input node");
     if (d.type == AD_FXN_OUTPUT) {
@@ -267,6 +288,16 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
       const ad_bitcrusher_config* c = node_cfg<ad_bitcrusher_config>(cfg, i);
       if (!c || ad_bitcrusher_validate(c) != AD_OK)
         AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: bitcrusher node without a valid config of its size");
+    }
+    if (d.type == AD_FXN_DEESSER) {
+      const ad_deesser_config* c = node_cfg<ad_deesser_config>(cfg, i);
+      if (!c || ad_deesser_validate(c) != AD_OK)
+        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: de-esser node without a valid config of its size");
+    }
+    if (d.type == AD_FXN_TRANSIENT) {
+      const ad_transient_config* c = node_cfg<ad_transient_config>(cfg, i);
+      if (!c || ad_transient_validate(c) != AD_OK)
+        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: transient shaper node without a valid config of its size");
     }
     if (d.type == AD_FXN_COMPRESSOR && (d.dyn_mode < 0 || d.dyn_mode > 2))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: bad dynamics mode");
@@ -415,6 +446,28 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
       FxOp op{FxOp::BITCRUSHER};
       op.dst = b;
       op.bitcrusher = bc;
+      g->ops.push_back(op);
+      continue;
+    }
+    if (d.type == AD_FXN_DEESSER) {
+      flush(g, gr);
+      ad_deesser* de = nullptr;
+      ck(ad_deesser_create(node_cfg<ad_deesser_config>(cfg, i), g->channels, g->device, &de));
+      g->deessers.emplace_back(de);
+      FxOp op{FxOp::DEESSER};
+      op.dst = b;
+      op.deesser = de;
+      g->ops.push_back(op);
+      continue;
+    }
+    if (d.type == AD_FXN_TRANSIENT) {
+      flush(g, gr);
+      ad_transient* ts = nullptr;
+      ck(ad_transient_create(node_cfg<ad_transient_config>(cfg, i), g->channels, g->device, &ts));
+      g->transients.emplace_back(ts);
+      FxOp op{FxOp::TRANSIENT};
+      op.dst = b;
+      op.transient = ts;
       g->ops.push_back(op);
       continue;
     }
@@ -575,6 +628,12 @@ void run(ad_fx_graph* g, double* d0, int64_t stride0, int64_t n, hipStream_t s) 
       case FxOp::BITCRUSHER:
         ck(ad_bitcrusher_process_device(op.bitcrusher, dst, st(op.dst), n, ls));
         break;
+      case FxOp::DEESSER:
+        ck(ad_deesser_process_device(op.deesser, dst, st(op.dst), n, ls));
+        break;
+      case FxOp::TRANSIENT:
+        ck(ad_transient_process_device(op.transient, dst, st(op.dst), n, ls));
+        break;
     }
     if (op.signal) AD_HIP(hipEventRecord(g->op_ev[i], ls));
   }
@@ -669,6 +728,8 @@ int ad_fx_graph_reset(ad_fx_graph* g) {
     for (auto& f : g->ringmods) ck(ad_ringmod_reset(f.get()));
     for (auto& f : g->distortions) ck(ad_distortion_reset(f.get()));
     for (auto& f : g->bitcrushers) ck(ad_bitcrusher_reset(f.get()));
+    for (auto& f : g->deessers) ck(ad_deesser_reset(f.get()));
+    for (auto& f : g->transients) ck(ad_transient_reset(f.get()));
   });
 }
 

@@ -555,7 +555,11 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
  *   AD_FXN_DISTORTION  effects.Distortion.ProcessInPlace (distortion and
  *                      dist-cheb, runtime_modulation.go:91-171) and
  *   AD_FXN_BITCRUSHER  effects.BitCrusher.ProcessInPlace (bitcrusher,
- *                      runtime_modulation.go:71-89), configured through
+ *                      runtime_modulation.go:71-89),
+ *   AD_FXN_DEESSER     dynamics.DeEsser.ProcessInPlace (dyn-deesser,
+ *                      runtime_dynamics.go:240-314) and
+ *   AD_FXN_TRANSIENT   dynamics.TransientShaper.ProcessInPlace (dyn-transient,
+ *                      runtime_dynamics.go:316-351), configured through
  *                      ad_fx_graph_create_cfg.
  * The result is the output node's buffer.  Linear runs of in-place nodes fuse
  * into one launch (bit-identical, see capi_fxgraph.cpp).  Other node types
@@ -581,6 +585,9 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
 /* 14 is not assigned: it stays AD_ERR_UNKNOWN_EFFECT */
 #define AD_FXN_DISTORTION 15 /* distortion and dist-cheb: an ad_distortion created from cfg[i], an op of its own */
 #define AD_FXN_BITCRUSHER 16 /* bitcrusher: an ad_bitcrusher created from cfg[i], an op of its own */
+/* 17 is not assigned: it stays AD_ERR_UNKNOWN_EFFECT */
+#define AD_FXN_DEESSER 18   /* dyn-deesser: an ad_deesser created from cfg[i], an op of its own */
+#define AD_FXN_TRANSIENT 19 /* dyn-transient: an ad_transient created from cfg[i], an op of its own */
 #define AD_FX_MAX_PARENTS 8
 struct ad_fdn_config;
 struct ad_delay_config;
@@ -624,11 +631,12 @@ int ad_fx_graph_create(const ad_fx_node* nodes, int n_nodes, int channels, int d
 int ad_fx_graph_create_ext(const ad_fx_node* nodes, const ad_fx_node_ext* ext, int n_nodes, int channels, int device,
                            ad_fx_graph** out);
 /* The configuration transport of the node types after RINGMOD: cfg[i] belongs to nodes[i] and holds the
- * node type's own config structure (DISTORTION: ad_distortion_config, BITCRUSHER: ad_bitcrusher_config) with
- * its size, so a later node type needs neither a new structure nor a new entry point.  cfg NULL: none, which
- * is ad_fx_graph_create_ext.  A DISTORTION or BITCRUSHER node without its configuration, with bytes other
- * than the size of its structure, or with a configuration its validate refuses is AD_ERR_INVALID_ARGUMENT,
- * through all three entry points.  The configurations are copied at create. */
+ * node type's own config structure (DISTORTION: ad_distortion_config, BITCRUSHER: ad_bitcrusher_config,
+ * DEESSER: ad_deesser_config, TRANSIENT: ad_transient_config) with its size, so a later node type needs
+ * neither a new structure nor a new entry point.  cfg NULL: none, which is ad_fx_graph_create_ext.  A
+ * DISTORTION, BITCRUSHER, DEESSER or TRANSIENT node without its configuration, with bytes other than the
+ * size of its structure, or with a configuration its validate refuses is AD_ERR_INVALID_ARGUMENT, through
+ * all three entry points.  The configurations are copied at create. */
 typedef struct ad_fx_node_cfg {
   const void* config;
   int64_t bytes;
@@ -1091,6 +1099,110 @@ int ad_bitcrusher_process(ad_bitcrusher* b, double* buf, int64_t n);
 int ad_bitcrusher_process_device(ad_bitcrusher* b, double* d_buf, int64_t stride, int64_t n, void* stream);
 int ad_bitcrusher_reset(ad_bitcrusher* b);
 void ad_bitcrusher_destroy(ad_bitcrusher* b);
+
+/* ---- dynamics.TransientShaper, dynamics.DeEsser (dsp/effects/dynamics/
+ * transient_shaper.go, deesser.go) --------------------------------------------
+ * For `channels` instances sharing one configuration.  In both only the
+ * envelope (in the de-esser behind its detection cascade) is serial in time;
+ * it runs one channel per lane in the reference's own operations and branch
+ * forms, so the envelope, the transient shaper's output and the de-esser's
+ * listen output are bit for bit the reference's.  Everything after env[t] is a
+ * pointwise pass.  The de-esser's gain (calculateGain :513-557) differs from
+ * the reference by the device math library's log and exp2 only, and Process is
+ * bit for bit the reference's given ad_deesser_gain.
+ * config: a *_coeff of 0 means "derive it with the C library's exp"
+ *   (timeMsToCoeff transient_shaper.go:184-200, updateTimeConstants
+ *   deesser.go:573-576); another value is the caller's own, for a caller whose
+ *   exp is not the C library's.  get_config reports the coefficients in use.
+ *   De-esser: mode 0 split band / 1 wideband, detector 0 bandpass / 1 highpass,
+ *   listen 0 / 1, filter_order 1..4.
+ * validate: the setters' own ranges (transient_shaper.go:14-19, 57-117;
+ *   deesser.go:57-72, 228-409), the de-esser's frequency below fs / 2 (:235,
+ *   :399); host only.
+ * set_param: the named setter with its own check; the int parameters take a
+ *   whole number.  A rejected value changes nothing.  The setters that end in
+ *   updateCoefficients / updateTimeConstants derive both envelope coefficients
+ *   again, as the reference does.  De-esser SAMPLE_RATE, FREQ, Q, DETECTOR and
+ *   FILTER_ORDER run rebuildFilters :578-622: both cascades' states are zeroed,
+ *   the envelope and the metrics stay.
+ * derived: on a config, host only, no device needed: the coefficients in use;
+ *   de-esser also section[5] = {b0, b1, b2, a1, a2} of every stage of both
+ *   cascades, bandNorm, thresholdLog2, kneeWidthLog2, rangeLin.
+ * kernel_info: channels per workgroup, samples staged per chunk and LDS bytes
+ *   of the walk the next call runs; de-esser: the cascades it walks.  One
+ *   stands for both while their states are equal; a listen or wideband call
+ *   advances detectFilters alone, after which split-band calls walk two until
+ *   a rebuild or Reset.
+ * get_state / set_state: one channel's envelope; de-esser: also detect[4][2]
+ *   and band[4][2], {d0, d1} of each section.
+ * ad_deesser_metrics: GetMetrics :499 of `channel`; reset_metrics :504.
+ * ad_deesser_gain: gains[i] = calculateGain(levels[i]) for host arrays [n], by
+ *   the device code a call runs.  Nothing advances.
+ * process / process_device / reset: as ad_fdn's.  Reset: transient shaper
+ *   :135-137 (the envelope), de-esser :485-496 (envelope, cascades, metrics). */
+typedef struct ad_transient ad_transient;
+typedef struct ad_transient_config {
+  double sample_rate, attack_amount, sustain_amount, attack_ms, release_ms, attack_coeff, release_coeff;
+} ad_transient_config;
+#define AD_TRANSIENT_SAMPLE_RATE 0    /* SetSampleRate transient_shaper.go:107 */
+#define AD_TRANSIENT_ATTACK_AMOUNT 1  /* SetAttackAmount transient_shaper.go:57 */
+#define AD_TRANSIENT_SUSTAIN_AMOUNT 2 /* SetSustainAmount transient_shaper.go:69 */
+#define AD_TRANSIENT_ATTACK 3         /* SetAttack transient_shaper.go:81 */
+#define AD_TRANSIENT_RELEASE 4        /* SetRelease transient_shaper.go:94 */
+#define AD_TRANSIENT_ATTACK_COEFF 5   /* attackCoeff, a caller's own */
+#define AD_TRANSIENT_RELEASE_COEFF 6  /* releaseCoeff, a caller's own */
+void ad_transient_default_config(ad_transient_config* cfg, double sample_rate);
+int ad_transient_validate(const ad_transient_config* cfg);
+int ad_transient_derived(const ad_transient_config* cfg, double* attack_coeff, double* release_coeff);
+int ad_transient_create(const ad_transient_config* cfg, int channels, int device, ad_transient** out);
+int ad_transient_set_param(ad_transient* t, int which, double value);
+int ad_transient_get_config(const ad_transient* t, ad_transient_config* cfg);
+int ad_transient_kernel_info(const ad_transient* t, int* channels_per_workgroup, int* tile, int* lds_bytes);
+int ad_transient_get_state(ad_transient* t, int channel, double* envelope);
+int ad_transient_set_state(ad_transient* t, int channel, double envelope);
+int ad_transient_process(ad_transient* t, double* buf, int64_t n);
+int ad_transient_process_device(ad_transient* t, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_transient_reset(ad_transient* t);
+void ad_transient_destroy(ad_transient* t);
+
+typedef struct ad_deesser ad_deesser;
+typedef struct ad_deesser_config {
+  double sample_rate, freq_hz, q, threshold_db, ratio, knee_db, attack_ms, release_ms, range_db, attack_coeff,
+      release_coeff;
+  int mode, detector, listen, filter_order;
+} ad_deesser_config;
+#define AD_DEESSER_SAMPLE_RATE 0   /* SetSampleRate deesser.go:394 */
+#define AD_DEESSER_FREQ 1          /* SetFrequency deesser.go:228 */
+#define AD_DEESSER_Q 2             /* SetQ deesser.go:248 */
+#define AD_DEESSER_THRESHOLD 3     /* SetThreshold deesser.go:263 */
+#define AD_DEESSER_RATIO 4         /* SetRatio deesser.go:276 */
+#define AD_DEESSER_KNEE 5          /* SetKnee deesser.go:291 */
+#define AD_DEESSER_ATTACK 6        /* SetAttack deesser.go:306 */
+#define AD_DEESSER_RELEASE 7       /* SetRelease deesser.go:321 */
+#define AD_DEESSER_RANGE 8         /* SetRange deesser.go:336 */
+#define AD_DEESSER_ATTACK_COEFF 9  /* attackCoeff, a caller's own */
+#define AD_DEESSER_RELEASE_COEFF 10 /* releaseCoeff, a caller's own */
+#define AD_DEESSER_MODE 11         /* SetMode deesser.go:350 */
+#define AD_DEESSER_DETECTOR 12     /* SetDetector deesser.go:361 */
+#define AD_DEESSER_LISTEN 13       /* SetListen deesser.go:375 */
+#define AD_DEESSER_FILTER_ORDER 14 /* SetFilterOrder deesser.go:381 */
+void ad_deesser_default_config(ad_deesser_config* cfg, double sample_rate);
+int ad_deesser_validate(const ad_deesser_config* cfg);
+int ad_deesser_derived(const ad_deesser_config* cfg, double* section, double* band_norm, double* threshold_log2,
+                       double* knee_width_log2, double* range_lin, double* attack_coeff, double* release_coeff);
+int ad_deesser_create(const ad_deesser_config* cfg, int channels, int device, ad_deesser** out);
+int ad_deesser_set_param(ad_deesser* d, int which, double value);
+int ad_deesser_get_config(const ad_deesser* d, ad_deesser_config* cfg);
+int ad_deesser_kernel_info(const ad_deesser* d, int* channels_per_workgroup, int* tile, int* lds_bytes, int* cascades);
+int ad_deesser_get_state(ad_deesser* d, int channel, double* envelope, double* detect, double* band);
+int ad_deesser_set_state(ad_deesser* d, int channel, double envelope, const double* detect, const double* band);
+int ad_deesser_metrics(ad_deesser* d, int channel, double* detection_level, double* gain_reduction);
+int ad_deesser_reset_metrics(ad_deesser* d);
+int ad_deesser_gain(ad_deesser* d, const double* levels, double* gains, int64_t n);
+int ad_deesser_process(ad_deesser* d, double* buf, int64_t n);
+int ad_deesser_process_device(ad_deesser* d, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_deesser_reset(ad_deesser* d);
+void ad_deesser_destroy(ad_deesser* d);
 
 /* ---- spectral correlation / deconvolution (dsp/conv/correlate.go,
  * dsp/conv/deconvolve.go) --------------------------------------
