@@ -14,13 +14,74 @@ in Chain.spec the way its stand-alone GPU test builds it:
              and ramps) or, mode 1, delayfx_ref.SimpleDelay of delay_samples
     flanger  delayfx_ref.Flanger
     phaser, tremolo, ringmod   modfx_ref.Phaser / Tremolo / RingModulator
+    distortion  shaper_ref.Distortion of the config's fields (the distortion and dist-cheb nodes)
+    bitcrusher  shaper_ref.BitCrusher of the config's fields; `.ref` on its process is the instance, for a
+                test that hands a fractional depth's quantLevels over from the device (sync_q of
+                test_shaper_gpu.py)
+    deesser     dynfx_ref.DeEsser through its setters
+    transient   dynfx_ref.TransientShaper through its setters
+                (both: attack_coeff / release_coeff 0 in the config means derived, as the library reads it; any
+                other value is the coefficient itself)
+
+Every runtime is [type, process, Reset]; Reset is the reference's own.
 """
 import numpy as np
 
 import delayfx_ref
+import dynfx_ref
 import fdn_ref
 import modfx_ref
 import oracle_lib as O
+import shaper_ref
+
+
+def host_spec(json_graph, fs, designer):
+    """Chain.spec of a graph without a device handle, for the node types of the newer named graphs
+    (tests/fxgraph_topologies.py NEWER): what Chain.LoadGraph records for them, from the same functions of
+    algodsp.effectchain.  The GPU suite holds it against Chain.spec itself."""
+    from algodsp import effectchain as E
+
+    g = E.parse_graph(json_graph)
+    order = [E.INPUT_NODE_ID] + [k for k in g.Order if k != E.INPUT_NODE_ID]
+    idx = {k: i for i, k in enumerate(order)}
+    spec = []
+    for k in order:
+        p, t = g.Nodes[k], g.Nodes[k].Type
+        split = lambda q: g.Nodes[order[q]].Type == E.NODE_TYPE_SPLIT_FREQ
+        sd = {"id": k, "bypassed": bool(p.Bypassed),
+              "parents": [(idx[e[0]], 1 if split(idx[e[0]]) and e[2] == 1 else 0) for e in g.Incoming[k]]}
+        fields = lambda cfg: {f: getattr(cfg, f) for f, _ in cfg._fields_}
+        if k == E.INPUT_NODE_ID:
+            sd["type"] = "input"
+        elif k == E.OUTPUT_NODE_ID:
+            sd["type"] = "output"
+        elif t == E.NODE_TYPE_SPLIT_FREQ:
+            lp, hp = E.split_freq_sections(p, fs)
+            sd.update(type="split", sections=lp, sections2=hp)
+        elif t in ("split", "sum"):
+            sd["type"] = "pass"
+        elif t in E.FILTER_TYPES:
+            sd.update(type="biquad", sections=([], 1.0))
+            if not p.Bypassed:
+                secs, gain = E.filter_chain(p, fs, designer)
+                sd["sections"] = (list(secs), gain)
+        elif t == "dyn-compressor":
+            sd.update(type="comp", comp=fields(E.compressor_config(p, fs)))
+        elif t == "phaser":
+            sd.update(type="phaser", phaser=fields(E.phaser_params(p, fs)))
+        elif t in ("distortion", "dist-cheb"):
+            cfg = E.distortion_params(p, fs) if t == "distortion" else E.dist_cheb_params(p, fs)
+            sd.update(type="distortion", distortion=E._config_dict(cfg))
+        elif t == "bitcrusher":
+            sd.update(type="bitcrusher", bitcrusher=E._config_dict(E.bitcrusher_params(p, fs)))
+        elif t == "dyn-deesser":
+            sd.update(type="deesser", deesser=E._config_dict(E.deesser_params(p, fs)))
+        elif t == "dyn-transient":
+            sd.update(type="transient", transient=E._config_dict(E.transient_params(p, fs)))
+        else:
+            raise ValueError(f"host_spec: node type {t!r}")
+        spec.append(sd)
+    return spec
 
 
 class FxGraph(O.FxGraph):
@@ -61,7 +122,40 @@ class FxGraph(O.FxGraph):
             c = {k: v for k, v in d[t].items() if k not in ("sample_rate", "smoothing_coeff")}
             r = modfx_ref.KINDS[t](d[t]["sample_rate"], **c)
             return [t, r.process, r.Reset]
-        return super().node_runtime(d)
+        if t in ("distortion", "bitcrusher"):
+            c = dict(d[t])
+            kind = shaper_ref.Distortion if t == "distortion" else shaper_ref.BitCrusher
+            r = kind(c.pop("sample_rate"), **c)
+
+            def process(block):
+                return r.process_many(np.asarray(block, dtype=np.float64)[None, :])[0]
+
+            process.ref = r
+            return [t, process, r.Reset]
+        if t == "deesser":
+            c = d[t]
+            r = dynfx_ref.DeEsser(c["sample_rate"])
+            r.SetFrequency(c["freq_hz"]), r.SetQ(c["q"]), r.SetThreshold(c["threshold_db"]), r.SetRatio(c["ratio"])
+            r.SetKnee(c["knee_db"]), r.SetAttack(c["attack_ms"]), r.SetRelease(c["release_ms"]), r.SetRange(c["range_db"])
+            r.SetMode(c["mode"]), r.SetDetector(c["detector"]), r.SetFilterOrder(c["filter_order"])
+            r.SetListen(c["listen"] != 0)
+        elif t == "transient":
+            c = d[t]
+            r = dynfx_ref.TransientShaper(c["sample_rate"])
+            r.SetAttackAmount(c["attack_amount"]), r.SetSustainAmount(c["sustain_amount"])
+            r.SetAttack(c["attack_ms"]), r.SetRelease(c["release_ms"])
+        else:
+            return super().node_runtime(d)
+        if c["attack_coeff"] != 0:
+            r.attackCoeff = c["attack_coeff"]
+        if c["release_coeff"] != 0:
+            r.releaseCoeff = c["release_coeff"]
+
+        def process(block):
+            return r.ProcessInPlace(np.array(block, dtype=np.float64))
+
+        process.ref = r
+        return [t, process, r.Reset]
 
     def reset(self):
         """ad_fx_graph_reset: every node's own Reset.  The feedback delay's keeps

@@ -3,7 +3,8 @@ of topologies, against the one-channel reference interpreter
 (tests/fxgraph_ref.py) of Chain.Process.
 
 Every graph is a JSON graph through effectchain.Chain.LoadGraph, at 8 kHz
-unless it names a rate.  One handle takes four calls of 700, 1, 1500 and 64
+unless it names a rate (48 kHz wherever there is a de-esser, which cannot be
+built at 8 kHz).  One handle takes four calls of 700, 1, 1500 and 64
 samples with fresh noise per call and channel (the pool grows, is reallocated,
 and is then longer than the call), is Reset, and takes call 1 again: the
 interpreter's output after its own Reset, and call 1's output on the bits.  (A
@@ -15,36 +16,68 @@ The named graphs (tests/fxgraph_topologies.py: what each one aims at) run at 3
 and at 65 channels, and again through process_device on a side stream with a
 row stride of 2048 and no host synchronisation between the producer of the
 input, the graph and the consumer of the output: the same bits as the host
-path, and nothing written past the call's length.  The generated family runs
-at 3 channels.
+path, and nothing written past the call's length.  The generated families run
+at 3 channels: the first one's types end at ringmod; the second one adds the
+distortion, dist-cheb, bitcrusher, dyn-deesser and dyn-transient nodes, which
+the named graphs ending in _newer and newer_nodes_line aim at as well, at
+48 kHz.  Their input is bursts wherever a de-esser or a transient shaper has
+to work and to rest (tests/test_fxgraph_ref.py checks on the CPU that they
+do).
 
 Bars (the project's, test_fxgraph.py): relative RMS <= 1e-12 and max abs <
 1e-10 per checked channel; with a reverb-conv node (Large Church, latency 128)
 1e-7 and 1e-9; graphs whose nodes are all bit-exact against their references
 (filters, crossovers, Freeverb, delays, mixes: no dynamics, no modulated node,
-no convolution) are compared on the bits.
+no convolution) are compared on the bits.  The newer nodes are exact or not by
+their configuration (_exact): the transient shaper, the bit crusher at a whole
+bit depth, the distortion's algebraic modes, polynomial approximations and
+Chebyshev mode, and the de-esser with listen on are; the distortion's tanh,
+atan and exp modes and the working de-esser (log and exp2 of the device
+library) are not.  A bit crusher has only exact nodes upstream
+(fxgraph_topologies.py: the quantiser rule); at a fractional bit depth the
+device's quantLevels is compared with the restatement's first and handed over
+if it differs, as test_shaper_gpu.py's sync_q does.
 """
 import functools
+import json
 
 import numpy as np
 import pytest
 
 import fxgraph_ref
 import fxgraph_topologies as T
-from algodsp import design, effectchain as E, irlib, signals
+import shaper_ref
+from algodsp import _lib, design, effectchain as E, irlib, processors as P, signals
 
 pytestmark = pytest.mark.gpu
 
 CALLS = [700, 1, 1500, 64]
 STRIDE = 2048
 EXACT_KINDS = {"input", "output", "pass", "biquad", "split", "verb", "delay"}
+EXACT_MODES = {shaper_ref.MODES.index(m) for m in shaper_ref.ALGEBRAIC}
+POLY_MODES = {shaper_ref.MODES.index(m) for m in shaper_ref.POLY_ALGEBRAIC}
+
+
+def _exact(d):
+    """Whether spec node d is compared on the bits: by type, the newer nodes by configuration."""
+    t = d["type"]
+    if t == "transient":
+        return True
+    if t == "bitcrusher":
+        return d[t]["bit_depth"] == int(d[t]["bit_depth"])
+    if t == "distortion":
+        return d[t]["mode"] in EXACT_MODES or (d[t]["mode"] in POLY_MODES and d[t]["approx"] == shaper_ref.POLYNOMIAL)
+    if t == "deesser":
+        return d[t]["listen"] != 0
+    return t in EXACT_KINDS
 
 
 def _input(json_graph, k, c, n, pos):
     """Call k's block of channel c: noise of its own seed, scaled 0.5; bursts
-    where a gate or an expander has to open and close."""
+    where a gate or an expander has to open and close, a de-esser to reduce and
+    to recover, a transient shaper's envelope to rise and to fall."""
     x = signals.white_noise(n, 0x70B0 + 1000 * k + c)
-    if T.has_type(json_graph, "dyn-gate", "dyn-expander"):
+    if T.has_type(json_graph, "dyn-gate", "dyn-expander", "dyn-deesser", "dyn-transient"):
         return np.where(((pos + np.arange(n)) // 300) % 2 == 0, 0.6, 0.004) * x
     return 0.5 * x
 
@@ -66,6 +99,8 @@ def _chain(json_graph, fs, C):
 def _graph_of(name):
     if name in T.NAMED:
         return T.NAMED[name]
+    if name.startswith("2:"):  # the second family
+        return T.graph(*T.generate(int(name[2:]), family=2)), T.FS2
     return T.graph(*T.generate(int(name))), T.FS
 
 
@@ -92,7 +127,16 @@ def _expected(name, c):
     """The interpreter's four outputs for channel c, and call 1 again after its
     reset (channel c's input does not depend on the channel count)."""
     g, fs = _graph_of(name)
-    ref = fxgraph_ref.FxGraph(_host_run(name, 3)[3], fs)
+    spec = _host_run(name, 3)[3]
+    ref = fxgraph_ref.FxGraph(spec, fs)
+    for d, r in zip(spec, ref.rt):
+        if d["type"] == "bitcrusher" and not _exact(d):  # exp2 of a fractional depth: the device's, if it differs
+            h = P.BitCrusher(channels=1, config=_lib.BitCrusherConfig(**d["bitcrusher"]))
+            q, crusher = h.derived()["quant_levels"], r[1].ref
+            h.close()
+            print(f"{name}: bit depth {crusher.bitDepth}: quantLevels {crusher.quantLevels!r}, the device's {q!r}")
+            assert np.nextafter(crusher.quantLevels, 0.0) <= q <= np.nextafter(crusher.quantLevels, np.inf)
+            crusher.quantLevels = q
     xs = _inputs(g, [c])
     outs = [ref.process(x[0]) for x in xs]
     ref.reset()
@@ -102,7 +146,7 @@ def _expected(name, c):
 def _check(name, C, channels):
     outs, again, ops, spec = _host_run(name, C)
     kinds = {d["type"] for d in spec if d["type"] == "split" or not d["bypassed"]}  # what runs: a bypassed split does
-    exact = kinds <= EXACT_KINDS
+    exact = all(_exact(d) for d in spec if d["type"] == "split" or not d["bypassed"])
     rms_bar, abs_bar = (1e-7, 1e-9) if "conv" in kinds else (1e-12, 1e-10)
     for c in channels:
         for k, want in enumerate(_expected(name, c)):
@@ -136,11 +180,20 @@ def test_named_graph(gpu, name, C):
                                              "flanger", "phaser", "tremolo", "ringmod", "split"}
     if name == "diamond":
         assert ops[1] == 3  # B's copy of A's buffer, and the output's mix
+    if name == "newer_nodes_line":
+        assert {d["type"] for d in spec} == {"input", "output", "bitcrusher", "transient", "distortion", "deesser"}
+    if name == "fanin_newer":
+        assert ops[2] == 8  # 11 concurrent branches: three of them on the fallback lane i % 8
+    if name == "diamond_newer":
+        assert ops[:2] == T.DIAMOND_NEWER_OPS
+    if name in T.NEWER and C == 3:  # the spec the CPU tests of these graphs' inputs work from is the chain's
+        as_data = lambda sp: json.loads(json.dumps(sp))
+        assert as_data(fxgraph_ref.host_spec(*T.NAMED[name], design.RBJDesigner())) == as_data(spec)
 
 
-@pytest.mark.parametrize("seed", T.SEEDS)
+@pytest.mark.parametrize("seed", [str(s) for s in T.SEEDS] + [f"2:{s}" for s in T.SEEDS2])
 def test_generated_graph(gpu, seed):
-    _check(str(seed), 3, range(3))
+    _check(seed, 3, range(3))
 
 
 @pytest.mark.parametrize("name", list(T.NAMED))
