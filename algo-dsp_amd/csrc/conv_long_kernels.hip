@@ -13,10 +13,6 @@
 
 namespace adsp {
 
-template <int M, int V>
-constexpr int last_pass_ns() {
-  return FftPlan<M, V>::ns(FftPlan<M, V>::NPASS - 1);
-}
 constexpr int N1 = kLongN1, N2 = kLongN2, W = kLongW;
 constexpr int kColThreads = 256;
 constexpr int kRowsPerInstr = kColThreads / W;  // tile rows one load / store instruction covers
@@ -26,6 +22,13 @@ constexpr int RV = 8;  // values per thread of the row transform
 using RowPlan = FftPlan<N2, RV>;
 static_assert(ColPlan::T * (W / 2) == kColThreads, "a tile's transforms fill the workgroup");
 static_assert(N1 % kRowsPerInstr == 0, "whole load rounds");
+// A column transform is ColPlan::T lanes of one wave and its image is its own,
+// so the exchanges inside it order nothing across waves.  C syncs them at wave
+// scope (fft_run_wave) and keeps the two workgroup barriers that order
+// cross-wave traffic: after Z has gone into the images, and before the stores
+// read across them.  The same change was measured on A and gains nothing
+// there, so A keeps fft_run.
+static_assert(ColPlan::T <= 64 && 64 % ColPlan::T == 0, "a column transform sits inside one wave");
 
 __global__ __launch_bounds__(kColThreads) void k_long_cols_fwd(LongColArgs a) {
   __shared__ double2 lds[(W / 2) * FS];
@@ -119,12 +122,12 @@ __global__ __launch_bounds__(kColThreads) void k_long_cols_inv(LongColArgs a) {
   double2 v[16];
 #pragma unroll
   for (int s = 0; s < 16; ++s) v[s] = my[pass0_slot<N1, 16>(t, s)];
-  __syncthreads();
-  fft_run<N1, 16, false>(v, t, my, tw);
-  __syncthreads();
+  wave_lds_sync();
+  fft_run_wave<N1, 16, false>(v, t, my, tw);
+  wave_lds_sync();
 #pragma unroll
   for (int s = 0; s < 16; ++s) my[last_pass_slot<N1, 16>(t, s)] = v[s];
-  __syncthreads();
+  __syncthreads();  // the stores below read across the images
   // 8-byte stores, runs of W per row.  The per-row 16-byte pair scheme K3 uses
   // for rows off alignment was measured here and is slower (DESIGN.md §2:
   // C 154 us against 124 us, the step 0.418 against 0.385 ms).
@@ -141,12 +144,43 @@ __global__ __launch_bounds__(kColThreads) void k_long_cols_inv(LongColArgs a) {
   }
 }
 
-// One row per workgroup of N2 / RV threads, RV values per thread.  The row's
-// pass-0 input order and its last pass's output order are both tid + T s, so
-// the forward transform's result feeds the inverse without a reshuffle.
+// One row per workgroup of N2 / RV threads, RV values per thread: the four
+// radix-8 Stockham passes of RowPlan, with the butterflies dealt to threads so
+// that one exchange per transform crosses waves.  Input digits n2 = 512 a3 +
+// 64 a2 + 8 a1 + a0, output digits k2 = k0 + 8 k1 + 64 k2' + 512 k3; a thread
+// is (wave; lane), its RV values the slot:
+//
+//   pass  forward thread        slot   inverse thread        slot
+//   0     (a2; 8 a1 + a0)       a3     (k0; 8 k1 + k2')      k3
+//   1     (k0; 8 a1 + a0)       a2     (k0; 8 k1 + m0)       k2'
+//   2     (k0; 8 k1 + a0)       a1     (k0; 8 m1 + m0)       k1
+//   3     (k0; 8 k1 + k2')      a0     (m2; 8 m1 + m0)       k0
+//
+// (m: the inverse's output digits, n2 = m0 + 8 m1 + 64 m2 + 512 m3.)  From the
+// forward pass 1 to the inverse pass 2 wave k0 works inside its own slice
+// lds[512 k0 ..]: those four exchanges sync at wave scope.  The forward pass 0
+// writes into the other waves' slices (nothing has read the image yet) and the
+// inverse pass 2 writes its own slice for pass 3 to read across: one workgroup
+// barrier each.  The forward result sits where the inverse's pass 0 wants it,
+// and the inverse's last pass is back at tid + T s, the order of the row's
+// loads and stores.  The butterflies, twiddle exponents and powering order are
+// RowPlan's (jb below is the plan's butterfly index); H rows are stored and
+// read positionally by this kernel alone, in the forward result's order.
+//
+// Slice addresses (tools/lds_conflicts.py: no conflicts): a read of slot r by
+// lane l is 64 r + l, or 64 r + (l ^ r) where the writers' eight-lane groups
+// run over the slot digit (forward pass 2 -> 3, inverse pass 0 -> 1).
 // BUILD: forward half only, the scaled spectrum stored to Hout (the IR's H rows).
 constexpr int kRowThreads = RowPlan::T;
-static_assert(last_pass_ns<N2, RV>() == kRowThreads, "k_long_rows relies on pass-0 order == last-pass order");
+static_assert(RowPlan::NPASS == 4 && RowPlan::R0 == RV && RV == 8 && kRowThreads == 8 * 64,
+              "k_long_rows: four radix-8 passes over eight waves of 64 lanes, wave = k0");
+
+// lane l's x in every lane (l known at compile time), through scalar registers
+__device__ __forceinline__ double wave_bcast(double x, int l) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
+  return __hiloint2double(hi, lo);
+}
 
 // two workgroups per CU: 2 N2 / RV / 64 waves over the CU's 4 SIMDs
 constexpr int kRowWavesPerSimd = 2 * kRowThreads / 256;
@@ -154,10 +188,12 @@ template <bool BUILD>
 __global__ __launch_bounds__(kRowThreads, kRowWavesPerSimd) void k_long_rows(LongRowArgs a) {
   __shared__ double2 lds[N2];
   __shared__ double2 ltab[TwSplit<N2>::N];
-  __shared__ double2 rtab[RV];
   __shared__ double2 wtab[kRowThreads];  // each thread's own W_N^(k1 tid), parked between its two uses
   constexpr int T = kRowThreads;
   const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l0 = lane & 7, l1 = lane & 56;
   const int item = xcd_remap(blockIdx.x, gridDim.x);
   const int ncb = a.blocks * a.channels;
   const int cb = item % ncb, k1 = item / ncb;  // block and channel fastest: co-resident items share H rows
@@ -166,31 +202,59 @@ __global__ __launch_bounds__(kRowThreads, kRowWavesPerSimd) void k_long_rows(Lon
 #pragma unroll
   for (int s = 0; s < RV; ++s) v[s] = ld2<true>(row + tid + T * s);
   const TwLds<N2> tw = tw_lds_compute<N2>(ltab, tid, T);
-  // W_N^(k1 n2), n2 = tid + T s: W_N^(k1 tid) * W_N^(T k1 s)
-  if (tid < RV) {
-    double sn, cs;
-    sincospi(-2.0 * (double)(T * k1 * tid) / (double)kLongN, &sn, &cs);
-    rtab[tid] = make_double2(cs, sn);
+  // W_N^(k1 n2), n2 = tid + T s: W_N^(k1 tid) * W_N^(T k1 s).  The second
+  // factor is the row's own; every wave computes it in its lanes 0 .. RV-1 and
+  // hands it round in scalar registers, so no barrier stands before pass 0.
+  double2 rt[RV];
+  {
+    double2 r;
+    sincospi(-2.0 * (double)(T * k1 * l0) / (double)kLongN, &r.y, &r.x);
+#pragma unroll
+    for (int s = 0; s < RV; ++s) rt[s] = make_double2(wave_bcast(r.x, s), wave_bcast(r.y, s));
   }
   {
     double2 w0;
     sincospi(-2.0 * (double)(k1 * tid) / (double)kLongN, &w0.y, &w0.x);
     wtab[tid] = w0;
-    __syncthreads();
 #pragma unroll
-    for (int s = 0; s < RV; ++s) v[s] = c_mul(v[s], c_mul(w0, rtab[s]));
+    for (int s = 0; s < RV; ++s) v[s] = c_mul(v[s], c_mul(w0, rt[s]));
   }
-  // the forward transform, with the H row's loads issued behind its first
-  // pass (v is free there): they land while the later passes run
-  pass_compute_store<N2, RV, 0, true>(v, tid, lds, tw);
+  // forward pass 0, value k0 into wave k0's slice; the H row's loads are
+  // issued behind it (v is free there) and land while the later passes run
+  Dft<RV, true>::run(v);
+#pragma unroll
+  for (int r = 0; r < RV; ++r) lds[T * r + tid] = v[r];
   double2 h[BUILD ? 1 : RV];
   if constexpr (!BUILD) {
     const double2* hrow = a.H + ((int64_t)a.ir_index[cb / a.blocks] * kLongRows + k1) * kLongPitch;
 #pragma unroll
     for (int s = 0; s < RV; ++s) h[s] = hrow[tid + T * s];
   }
-  run_middle_passes<N2, RV, true, 1>(v, tid, lds, tw);
-  last_pass_compute<N2, RV, true>(v, tid, tw);  // v[s] = X[k1 + N1 (tid + T s)]
+  __syncthreads();  // the slices are whole; ltab is filled
+  double2* sl = lds + 64 * RV * wv;
+  double2 w = twiddle_root<N2, RV, 8, true>(wv, tw);  // jb = 64 a1 + 8 a0 + k0
+#pragma unroll
+  for (int r = 0; r < RV; ++r) v[r] = sl[64 * r + lane];
+  twiddle_powers<RV>(v, w);
+  Dft<RV, true>::run(v);
+  wave_lds_sync();
+#pragma unroll
+  for (int r = 0; r < RV; ++r) sl[8 * l1 + 8 * r + l0] = v[r];  // 64 a1 + 8 k1 + a0
+  w = twiddle_root<N2, RV, 64, true>(l1 + wv, tw);  // jb = 64 a0 + 8 k1 + k0
+  wave_lds_sync();
+#pragma unroll
+  for (int r = 0; r < RV; ++r) v[r] = sl[64 * r + lane];
+  twiddle_powers<RV>(v, w);
+  Dft<RV, true>::run(v);
+  wave_lds_sync();
+#pragma unroll
+  for (int r = 0; r < RV; ++r) sl[64 * l0 + ((l1 + r) ^ l0)] = v[r];  // 64 a0 + ((8 k1 + k2') ^ a0)
+  w = twiddle_root<N2, RV, 512, true>(64 * l0 + l1 + wv, tw);  // jb = 64 k2' + 8 k1 + k0
+  wave_lds_sync();
+#pragma unroll
+  for (int r = 0; r < RV; ++r) v[r] = sl[64 * r + (lane ^ r)];
+  twiddle_powers<RV>(v, w);
+  Dft<RV, true>::run(v);  // v[s] = X[k1 + N1 (wv + 8 (lane / 8) + 64 (lane % 8) + T s)]
   if constexpr (BUILD) {
     double2* out = a.Hout + ((int64_t)cb * kLongRows + k1) * kLongPitch;
 #pragma unroll
@@ -198,11 +262,37 @@ __global__ __launch_bounds__(kRowThreads, kRowWavesPerSimd) void k_long_rows(Lon
   } else {
 #pragma unroll
     for (int s = 0; s < RV; ++s) v[s] = c_mul(v[s], h[s]);
-    __syncthreads();
-    fft_run<N2, RV, false>(v, tid, lds, tw);
-    const double2 w0 = wtab[tid];
+    Dft<RV, false>::run(v);  // inverse pass 0
+    wave_lds_sync();
 #pragma unroll
-    for (int s = 0; s < RV; ++s) st2<true>(row + tid + T * s, c_mul(v[s], c_conj(c_mul(w0, rtab[s]))));
+    for (int r = 0; r < RV; ++r) sl[64 * l0 + ((l1 + r) ^ l0)] = v[r];  // 64 k2' + ((8 k1 + m0) ^ k2')
+    w = twiddle_root<N2, RV, 8, false>(l0, tw);  // jb = 64 k1 + 8 k0 + m0
+    wave_lds_sync();
+#pragma unroll
+    for (int r = 0; r < RV; ++r) v[r] = sl[64 * r + (lane ^ r)];
+    twiddle_powers<RV>(v, w);
+    Dft<RV, false>::run(v);
+    wave_lds_sync();
+#pragma unroll
+    for (int r = 0; r < RV; ++r) sl[8 * l1 + 8 * r + l0] = v[r];  // 64 k1 + 8 m1 + m0
+    w = twiddle_root<N2, RV, 64, false>(lane, tw);  // jb = 64 k0 + 8 m1 + m0
+    wave_lds_sync();
+#pragma unroll
+    for (int r = 0; r < RV; ++r) v[r] = sl[64 * r + lane];
+    twiddle_powers<RV>(v, w);
+    Dft<RV, false>::run(v);
+    wave_lds_sync();
+#pragma unroll
+    for (int r = 0; r < RV; ++r) sl[64 * r + lane] = v[r];  // own slice: 512 k0 + 64 m2 + 8 m1 + m0
+    w = twiddle_root<N2, RV, 512, false>(tid, tw);  // jb = 64 m2 + 8 m1 + m0
+    const double2 w0 = wtab[tid];
+    __syncthreads();  // pass 3 reads across the slices
+#pragma unroll
+    for (int r = 0; r < RV; ++r) v[r] = lds[T * r + tid];
+    twiddle_powers<RV>(v, w);
+    Dft<RV, false>::run(v);  // v[s] = y[tid + T s]
+#pragma unroll
+    for (int s = 0; s < RV; ++s) st2<true>(row + tid + T * s, c_mul(v[s], c_conj(c_mul(w0, rt[s]))));
   }
 }
 

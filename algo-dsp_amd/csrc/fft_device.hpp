@@ -411,6 +411,66 @@ __device__ __forceinline__ void fft_run(double2* v, int tid, double2* lds, const
   last_pass_compute<M, V, FWD, TW>(v, tid, twM);
 }
 
+// ---------------------------------------------------------------------------
+// Wave-contained exchanges.  One wave's LDS instructions execute in order, so
+// an exchange whose writers and readers are lanes of the same wave needs no
+// s_barrier: only the compiler has to keep the accesses on their side of the
+// sync.  wave_lds_sync() is __syncthreads() at wavefront scope (release fence,
+// wave barrier, acquire fence) and emits no instruction of its own.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// apply_twiddles in two halves, so a caller can issue the table read ahead of
+// the wait for the butterfly's data: twiddle_root reads W (conjugated for the
+// inverse), twiddle_powers multiplies v[r] by W^r in apply_twiddles' order.
+template <int M, int R, int NS, bool FWD, class TW>
+__device__ __forceinline__ double2 twiddle_root(int jb, const TW& tw) {
+  static_assert(NS > 1, "pass 0 has no twiddles");
+  const double2 w = tw((jb & (NS - 1)) * (M / (NS * R)));
+  return FWD ? w : c_conj(w);
+}
+template <int R>
+__device__ __forceinline__ void twiddle_powers(double2* v, double2 w) {
+  double2 wr = w;
+#pragma unroll
+  for (int r = 1; r < R; ++r) {
+    v[r] = c_mul(v[r], wr);
+    if (r + 1 < R) wr = c_mul(wr, w);
+  }
+}
+
+// run_middle_passes / fft_run for a transform whose Plan::T threads are lanes
+// of one wave (T <= 64, the transform's first thread on a multiple of T inside
+// the wave, its LDS image touched by no other wave meanwhile): the same
+// passes, arithmetic and LDS addresses, with wave_lds_sync() for each barrier.
+template <int M, int V, bool FWD, int P = 1, class TW>
+__device__ __forceinline__ void run_middle_passes_wave(double2* v, int tid, double2* lds, const TW& twM) {
+  using Plan = FftPlan<M, V>;
+  if constexpr (P < Plan::NPASS) {
+    wave_lds_sync();
+    pass_load<M, V, P>(v, tid, lds);
+    if constexpr (P + 1 < Plan::NPASS) {
+      wave_lds_sync();
+      pass_compute_store<M, V, P, FWD, TW>(v, tid, lds, twM);
+      run_middle_passes_wave<M, V, FWD, P + 1, TW>(v, tid, lds, twM);
+    }
+  }
+}
+template <int M, int V, bool FWD, class TW>
+__device__ __forceinline__ void fft_run_wave(double2* v, int tid, double2* lds, const TW& twM) {
+  using Plan = FftPlan<M, V>;
+  static_assert(Plan::T <= 64 && 64 % Plan::T == 0, "the transform's threads must sit inside one wave");
+  if constexpr (Plan::NPASS > 1) {
+    pass_compute_store<M, V, 0, FWD, TW>(v, tid, lds, twM);
+    run_middle_passes_wave<M, V, FWD, 1, TW>(v, tid, lds, twM);
+  }
+  last_pass_compute<M, V, FWD, TW>(v, tid, twM);
+}
+
 // fft_run for a workgroup where only some waves hold a transform: `active`
 // (wave-uniform) guards the arithmetic and the LDS traffic, while every wave
 // still takes each barrier of the passes (s_barrier counts all waves).

@@ -10,6 +10,8 @@ For every plan (M, V) at a workgroup of max(M/V, 256) threads, this prints the
 extra cycles per workgroup of its Stockham stores and loads plus the
 consecutive staging reads/writes, for the round-1 swizzle (AD_LDS_SWZ=0) and
 the round-5 one (AD_LDS_SWZ=1), with unpadded (M) and padded (M + 1) rows.
+Ahead of that table it prints the same figure for each exchange of the
+long-block row kernel, which addresses its wave slices directly.
 
   python3 tools/lds_conflicts.py
 """
@@ -75,7 +77,45 @@ def extra_cycles(pats, rowoff, f):
     return tot
 
 
+def long_rows_patterns(xor=True):
+    """k_long_rows (conv_long_kernels.hip): 512 threads, wave w owns the slice
+    at 512 w.  name -> the eight writes and eight reads of each exchange of the
+    forward (F) and inverse (I) transform; addresses are used as they are (no
+    lds_slot).  xor=False drops the l ^ r of the two exchanges whose writers'
+    eight-lane groups run over the slot digit, to show what it is for."""
+    out = {}
+    tids = range(512)
+    wv = lambda t: 512 * (t >> 6)
+    l0, l1, ln = (lambda t: t & 7), (lambda t: t & 56), (lambda t: t & 63)
+    x = (lambda a, b: a ^ b) if xor else (lambda a, b: a)
+    cross_w = lambda r: [(0, 512 * r + t) for t in tids]            # into / out of every slice
+    plain_r = lambda r: [(0, wv(t) + 64 * r + ln(t)) for t in tids]
+    mid_w = lambda r: [(0, wv(t) + 8 * l1(t) + 8 * r + l0(t)) for t in tids]
+    xor_w = lambda r: [(0, wv(t) + 64 * l0(t) + x(l1(t) + r, l0(t))) for t in tids]
+    xor_r = lambda r: [(0, wv(t) + 64 * r + x(ln(t), r)) for t in tids]
+    for name, w, r in [("F pass 0 -> 1 (workgroup)", cross_w, plain_r), ("F pass 1 -> 2", mid_w, plain_r),
+                       ("F pass 2 -> 3", xor_w, xor_r), ("I pass 0 -> 1", xor_w, xor_r),
+                       ("I pass 1 -> 2", mid_w, plain_r), ("I pass 2 -> 3 (workgroup)", plain_r, cross_w)]:
+        out[name] = [('w', w(s)) for s in range(8)] + [('r', r(s)) for s in range(8)]
+    return out
+
+
+def check_long_rows_exchange():
+    """Each exchange's writes cover the image once and its reads the same cells."""
+    for name, p in long_rows_patterns().items():
+        writes = [a for s in range(8) for (_, a) in p[s][1]]
+        reads = [a for s in range(8) for (_, a) in p[8 + s][1]]
+        assert sorted(writes) == sorted(reads) == list(range(4096)), name
+
+
 if __name__ == "__main__":
+    print("k_long_rows exchanges (extra LDS cycles per workgroup; without the lane ^ slot swizzle in brackets)")
+    check_long_rows_exchange()
+    ident = lambda i: i
+    plain = long_rows_patterns(False)
+    for name, p in long_rows_patterns().items():
+        print(f"  {name:28s} {extra_cycles(p, 0, ident):5d}  [{extra_cycles(plain[name], 0, ident)}]")
+    print()
     print(f"{'plan':>12}  {'rows':>5}  {'swz0':>6}  {'swz1':>6}   (extra LDS cycles per workgroup)")
     for M, V in [(8192, 8), (4096, 8), (2048, 8), (1024, 8), (512, 8), (256, 8), (256, 4), (1024, 4),
                  (4096, 16), (2048, 16), (1024, 16), (512, 16), (256, 16)]:
