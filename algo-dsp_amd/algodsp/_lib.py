@@ -173,6 +173,23 @@ class DeEsserConfig(C.Structure):
                [(n, C.c_int) for n in ("mode", "detector", "listen", "filter_order")]
 
 
+class SpecFreezeConfig(C.Structure):
+    """ad_specfreeze_config (include/algodsp.h); window points at frame_size coefficients."""
+
+    _fields_ = [("sample_rate", C.c_double), ("mix", C.c_double)] + \
+               [(n, C.c_int) for n in ("frame_size", "hop_size", "phase_mode", "frozen", "window_type")] + \
+               [("window", C.POINTER(C.c_double))]
+
+
+class PitchSpecConfig(C.Structure):
+    """ad_pitchspec_config (include/algodsp.h); window and resample_taps point at the caller's tables."""
+
+    _fields_ = [("sample_rate", C.c_double), ("pitch_ratio", C.c_double)] + \
+               [(n, C.c_int) for n in ("frame_size", "analysis_hop", "window_type", "resample_quality")] + \
+               [("window", C.POINTER(C.c_double)), ("resample_taps", C.POINTER(C.c_double)),
+                ("n_resample_taps", C.c_int64)]
+
+
 class FxNodeCfg(C.Structure):
     """ad_fx_node_cfg: a node's own config structure and its size."""
 
@@ -391,6 +408,12 @@ def _declare(L: C.CDLL) -> None:
         "ad_deesser_metrics": (C.c_int, [vp, C.c_int, c_double_p, c_double_p]),
         "ad_deesser_reset_metrics": (C.c_int, [vp]),
         "ad_deesser_gain": (C.c_int, [vp, c_double_p, c_double_p, i64]),
+        "ad_specfreeze_state": (C.c_int, [vp, c_double_p, c_double_p, C.POINTER(C.c_int)]),
+        "ad_specfreeze_norm": (C.c_int, [vp, c_double_p, i64]),
+        "ad_pitchspec_set_resample_taps": (C.c_int, [vp, c_double_p, i64]),
+        "ad_pitchspec_effective_ratio": (C.c_int, [vp, c_double_p]),
+        "ad_pitchspec_synthesis_hop": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "ad_pitchspec_path": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "ad_correlate_fft": (C.c_int, [c_double_p, i64, c_double_p, i64, c_double_p, C.c_int]),
         "ad_correlate_fft_device": (C.c_int, [vp, i64, vp, i64, vp, C.c_int, vp]),
         "ad_deconv_default_options": (DeconvOptionsC, []),
@@ -422,6 +445,21 @@ def _declare(L: C.CDLL) -> None:
             f"ad_{kind}_process": (C.c_int, [vp, c_double_p, i64]),
             f"ad_{kind}_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
             f"ad_{kind}_reset": (C.c_int, [vp]),
+            f"ad_{kind}_destroy": (None, [vp]),
+        })
+    for kind, cfg in (("specfreeze", SpecFreezeConfig), ("pitchspec", PitchSpecConfig)):
+        sig.update({  # the two STFT handles share these prototypes
+            f"ad_{kind}_default_config": (None, [C.POINTER(cfg), C.c_double]),
+            f"ad_{kind}_validate": (C.c_int, [C.POINTER(cfg)]),
+            f"ad_{kind}_create": (C.c_int, [C.POINTER(cfg), C.c_int, C.c_int, C.POINTER(vp)]),
+            f"ad_{kind}_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
+            f"ad_{kind}_set_frame": (C.c_int, [vp, C.c_int, c_double_p]),
+            f"ad_{kind}_set_window": (C.c_int, [vp, C.c_int, c_double_p]),
+            f"ad_{kind}_get_config": (C.c_int, [vp, C.POINTER(cfg)]),
+            f"ad_{kind}_process": (C.c_int, [vp, c_double_p, i64]),
+            f"ad_{kind}_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
+            f"ad_{kind}_reset": (C.c_int, [vp]),
+            f"ad_{kind}_profile": (C.c_int, [vp, C.c_int, c_double_p]),
             f"ad_{kind}_destroy": (None, [vp]),
         })
     # an older build selected through ALGODSP_LIB (A/B runs against a parent

@@ -15,14 +15,15 @@ ad_fx_graph_create (include/algodsp.h), which runs every node on the GPU;
 there is no CPU path.  Node types outside {filter*, dyn-compressor,
 dyn-limiter, dyn-gate, dyn-expander, dyn-deesser, dyn-transient,
 reverb-freeverb, reverb-fdn, reverb, reverb-conv, delay, delay-simple, flanger,
-phaser, tremolo, ringmod, distortion, dist-cheb, bitcrusher, split-freq, split,
-sum, _input, _output} raise
+phaser, tremolo, ringmod, distortion, dist-cheb, bitcrusher, spectral-freeze,
+pitch-spectral, split-freq, split, sum, _input, _output} raise
 UnknownEffect (the GPU runtime's ErrUnknownEffect).  The phaser, tremolo and
 ringmod nodes carry their configuration in a parallel array (_NodeExt,
 ad_fx_graph_create_ext); _Node keeps its layout.  The distortion, dist-cheb
 and bitcrusher nodes carry theirs as (structure, size) in a second parallel
-array (FxNodeCfg, ad_fx_graph_create_cfg), and so do dyn-deesser and
-dyn-transient.
+array (FxNodeCfg, ad_fx_graph_create_cfg), and so do dyn-deesser,
+dyn-transient, spectral-freeze and pitch-spectral (whose structures point at the
+Hann table and the resampling prototype computed here).
 """
 from __future__ import annotations
 
@@ -34,8 +35,8 @@ import numpy as np
 
 from . import design
 from ._lib import (BitCrusherConfig, CompressorConfig, DeEsserConfig, DelayConfig, DistortionConfig, FdnConfig,
-                   FlangerConfig, FxNodeCfg, PhaserConfig, RingModConfig, TransientConfig, TremoloConfig, check, lib,
-                   ptr)
+                   FlangerConfig, FxNodeCfg, PhaserConfig, PitchSpecConfig, RingModConfig, SpecFreezeConfig,
+                   TransientConfig, TremoloConfig, check, lib, ptr)
 from .processors import section_table
 
 INPUT_NODE_ID = "_input"  # graph.go:10-13
@@ -48,6 +49,7 @@ FXN_DELAY, FXN_FLANGER = 9, 10
 FXN_PHASER, FXN_TREMOLO, FXN_RINGMOD = 11, 12, 13
 FXN_DISTORTION, FXN_BITCRUSHER = 15, 16  # 14 is not assigned
 FXN_DEESSER, FXN_TRANSIENT = 18, 19  # 17 is not assigned
+FXN_SPECFREEZE, FXN_PITCHSPEC = 20, 21
 MAX_PARENTS = 8
 
 FILTER_TYPES = ("filter", "filter-lowpass", "filter-highpass", "filter-bandpass", "filter-notch",
@@ -428,6 +430,71 @@ def transient_params(p: Params, fs: float) -> TransientConfig:
     return c
 
 
+def sanitize_spectral_frame_size(n: int) -> int:
+    """sanitizeSpectralPitchFrameSize (configure.go:563-593): [256, 4096], the nearer power of two, a tie to the lower."""
+    if n < 256:
+        return 256
+    if n > 4096:
+        return 4096
+    if n & (n - 1) == 0:
+        return n
+    lower = 256
+    while lower < n:
+        lower <<= 1
+    upper = lower
+    lower = max(lower >> 1, 256)
+    return lower if n - lower <= upper - n else upper
+
+
+def _spectral_frame_hop(p: Params):
+    """The frame and hop both spectral runtimes derive (runtime_filter_pitch_reverb.go:253-259, 279-285)."""
+    frame = sanitize_spectral_frame_size(int(_go_round(p.GetNum("frameSize", 1024))))
+    hop = max(int(_go_round(float(frame) * clamp(p.GetNum("hopRatio", 0.25), 0.01, 0.99))), 1)
+    if hop >= frame:
+        hop = frame - 1
+    return frame, hop
+
+
+def spectral_freeze_params(p: Params, fs: float):
+    """spectralFreezeRuntime.Configure (runtime_filter_pitch_reverb.go:278-299) and configureSpectralFreeze
+    (configure.go:391-433) on a NewSpectralFreeze(fs): (config, its Hann table).  phaseMode as
+    normalizeSpectralFreezePhaseMode reads it (normalize.go:174-183: anything but "hold" advances)."""
+    from .processors import WindowHann, spectral_window
+
+    c = SpecFreezeConfig()
+    c.sample_rate = float(fs)
+    c.frame_size, c.hop_size = _spectral_frame_hop(p)
+    c.mix = clamp(p.GetNum("mix", 1), 0, 1)
+    c.phase_mode = 0 if p.Str.get("phaseMode") == "hold" else 1
+    c.frozen = 1 if p.GetNum("frozen", 1) >= 0.5 else 0
+    c.window_type = WindowHann
+    w = spectral_window(WindowHann, c.frame_size)
+    c.window = ptr(w)
+    return c, w
+
+
+def spectral_pitch_params(p: Params, fs: float):
+    """spectralPitchRuntime.Configure (runtime_filter_pitch_reverb.go:252-268) and configureSpectralPitch
+    (configure.go:372-389) on a NewSpectralPitchShifter(fs): (config, its Hann table, the resampling
+    prototype of the time stretch or None)."""
+    from .processors import WindowHann, pitchspec_resample_taps, spectral_window
+
+    c = PitchSpecConfig()
+    c.sample_rate = float(fs)
+    c.pitch_ratio = 2.0 ** (clamp(p.GetNum("semitones", 0), -24, 24) / 12.0)  # SetPitchSemitones
+    c.frame_size, c.analysis_hop = _spectral_frame_hop(p)
+    c.window_type = WindowHann
+    c.resample_quality = 1  # resample.QualityBalanced, NewSpectralPitchShifter's
+    w = spectral_window(WindowHann, c.frame_size)
+    c.window = ptr(w)
+    taps = None
+    shop = max(int(_go_round(float(c.analysis_hop) * c.pitch_ratio)), 1)  # updateSynthesisHop
+    if abs(c.pitch_ratio - 1) > 0.15 and shop != c.analysis_hop:
+        taps = pitchspec_resample_taps(c.analysis_hop, shop, c.resample_quality)
+        c.resample_taps, c.n_resample_taps = ptr(taps), taps.size
+    return c, w, taps
+
+
 def _config_dict(cfg) -> dict:
     """A config structure's fields as plain data (arrays as lists)."""
     return {f: (list(getattr(cfg, f)) if isinstance(getattr(cfg, f), C.Array) else getattr(cfg, f))
@@ -694,6 +761,21 @@ class Chain:
                 keep.append(cfg)
                 cfgs[i].config, cfgs[i].bytes = C.addressof(cfg), C.sizeof(cfg)
                 sd.update(type="transient", transient=_config_dict(cfg))
+            elif t == "spectral-freeze":
+                d.type = FXN_SPECFREEZE
+                cfg, win = spectral_freeze_params(p, fs)
+                check(lib().ad_specfreeze_validate(C.byref(cfg)))
+                keep += [cfg, win]
+                cfgs[i].config, cfgs[i].bytes = C.addressof(cfg), C.sizeof(cfg)
+                sd.update(type="specfreeze", specfreeze={f: getattr(cfg, f) for f, _ in cfg._fields_ if f != "window"})
+            elif t == "pitch-spectral":
+                d.type = FXN_PITCHSPEC
+                cfg, win, taps = spectral_pitch_params(p, fs)
+                check(lib().ad_pitchspec_validate(C.byref(cfg)))
+                keep += [cfg, win, taps]
+                cfgs[i].config, cfgs[i].bytes = C.addressof(cfg), C.sizeof(cfg)
+                sd.update(type="pitchspec", pitchspec={f: getattr(cfg, f) for f, _ in cfg._fields_
+                                                       if f not in ("window", "resample_taps")})
             elif t in ("reverb-freeverb", "reverb"):  # reverbRuntime without model "fdn" is Freeverb
                 d.type = FXN_FREEVERB
                 for j, v in enumerate(freeverb_params(p)):

@@ -16,6 +16,8 @@ like the reference's own tests:
   effects.BitCrusher             dsp/effects/bit_crusher.go
   dynamics.TransientShaper       dsp/effects/dynamics/transient_shaper.go
   dynamics.DeEsser               dsp/effects/dynamics/deesser.go
+  effects.SpectralFreeze         dsp/effects/spectral_freeze.go
+  pitch.SpectralPitchShifter     dsp/effects/pitch/pitch_shift_spectral.go
   fir.Filter                     dsp/filter/fir/filter.go
   effectchain filter -> dyn-compressor -> reverb-freeverb (EffectChain)
 
@@ -29,8 +31,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (BitCrusherConfig, CompressorConfig, DeEsserConfig, DelayConfig, DistortionConfig, FdnConfig,
-                   FlangerConfig, PhaserConfig, RingModConfig, TransientConfig, TremoloConfig, check, f64, lib, ptr)
+from ._lib import (AD_ERR_INVALID_ARGUMENT, BitCrusherConfig, CompressorConfig, DeEsserConfig, DelayConfig,
+                   DistortionConfig, ErrInvalidArgument, FdnConfig, FlangerConfig, PhaserConfig, PitchSpecConfig,
+                   RingModConfig, SpecFreezeConfig, TransientConfig, TremoloConfig, check, f64, lib, ptr)
 
 DEVICE = 0
 SEC_STRIDE = 6  # {pre_gain, b0, b1, b2, a1, a2}
@@ -1197,6 +1200,257 @@ class DeEsser(_DynHandle):
         out = np.empty_like(lv)
         check(lib().ad_deesser_gain(self._h, ptr(lv), ptr(out), int(lv.size)))
         return out.reshape(np.shape(levels))
+
+
+# window.Type (dsp/window/window.go:12-16) of the windows the STFT processors take
+WindowRectangular, WindowHann, WindowHamming, WindowBlackman = range(4)
+_WINDOW_COEFFS = {  # fixedCosineWindowCoeffs (window.go:283-286, tables.go:4-6)
+    WindowHann: (0.5, -0.5),
+    WindowHamming: (0.54, -0.46),
+    WindowBlackman: (0.42, -0.5, 0.08),
+}
+
+
+def spectral_window(window_type: int, n: int) -> np.ndarray:
+    """window.Generate(t, n, WithPeriodic()) (window.go:140-162) for the
+    rectangular, Hann, Hamming and Blackman types: samplePosition i / n
+    (:404-415), cosineFromCoeffs (:393-402).  Any other type raises."""
+    t = int(window_type)
+    if t == WindowRectangular:
+        return np.ones(n)
+    if t not in _WINDOW_COEFFS:
+        raise ValueError(f"window type {window_type} is not supported by the STFT processors")
+    x = np.arange(n, dtype=np.float64) / float(n) if n > 1 else np.zeros(n)
+    phase = 2 * np.pi * x
+    s = np.zeros(n)
+    for k, c in enumerate(_WINDOW_COEFFS[t]):
+        s = s + c * np.cos(float(k) * phase)
+    return s
+
+
+class _StftHandle(_Handle):
+    """What SpectralFreeze and SpectralPitchShifter share: the frame size and
+    the window, whose table this layer computes, and the Process forms."""
+
+    _config = None
+
+    def _set(self, which: int, v):
+        check(self._fn("set_param")(self._h, which, float(v)))
+
+    def config(self):
+        cfg = self._config()
+        check(self._fn("get_config")(self._h, C.byref(cfg)))
+        return cfg
+
+    def SetSampleRate(self, v):
+        self._set(0, v)
+
+    def SetFrameSize(self, size: int):
+        size = int(size)
+        if size < 64 or size & (size - 1):  # the table needs a valid size; the library repeats the check
+            raise ErrInvalidArgument(AD_ERR_INVALID_ARGUMENT, f"frame size must be power-of-two and >= 64: {size}")
+        w = spectral_window(self.WindowType(), size)
+        check(self._fn("set_frame")(self._h, size, ptr(w)))
+
+    def SetWindowType(self, window_type: int):
+        w = spectral_window(window_type, self.FrameSize())
+        check(self._fn("set_window")(self._h, int(window_type), ptr(w)))
+
+    def SampleRate(self) -> float:
+        return self.config().sample_rate
+
+    def FrameSize(self) -> int:
+        return self.config().frame_size
+
+    def WindowType(self) -> int:
+        return self.config().window_type
+
+    def Process(self, x) -> np.ndarray:
+        out = f64(x).copy()
+        if out.size:
+            self.ProcessInPlace(out)
+        return out
+
+    PASSES = ("analysis", "walk", "synthesis", "overlap_add", "resample", "fused_frames")  # AD_STFT_PASS_*
+
+    def profile(self, enable: bool, read: bool = False):
+        """ad_*_profile: switch the per-pass event timing on or off; with `read`, the milliseconds per pass
+        of the calls made while it was on."""
+        ms = np.zeros(len(self.PASSES))
+        check(self._fn("profile")(self._h, 1 if enable else 0, ptr(ms) if read else None))
+        return dict(zip(self.PASSES, ms.tolist())) if read else None
+
+
+class SpectralFreeze(_StftHandle):
+    """effects.SpectralFreeze (spectral_freeze.go:36-414) for `channels`
+    instances sharing one configuration: NewSpectralFreeze(sample_rate) with
+    options as keywords (frame_size, hop_size, mix, phase_mode, frozen,
+    window_type).  One call handles a whole buffer.  A rejected setter value
+    raises ErrInvalidArgument and changes nothing."""
+
+    PhaseHold, PhaseAdvance = 0, 1  # SpectralFreezePhaseMode :23-28
+    P_SAMPLE_RATE, P_HOP, P_MIX, P_PHASE_MODE, P_FROZEN = range(5)  # AD_SPECFREEZE_*
+    _kind = "specfreeze"
+    _config = SpecFreezeConfig
+
+    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, **options):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        cfg = SpecFreezeConfig()
+        lib().ad_specfreeze_default_config(C.byref(cfg), float(sample_rate))
+        for k, v in options.items():
+            if k in ("frame_size", "hop_size", "phase_mode", "frozen", "window_type"):
+                setattr(cfg, k, int(v))
+            elif k == "mix":
+                cfg.mix = float(v)
+            else:
+                raise TypeError(f"unknown spectral freeze option {k!r}")
+        w = spectral_window(cfg.window_type, max(cfg.frame_size, 0))
+        cfg.window = ptr(w)
+        check(lib().ad_specfreeze_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+
+    def SetHopSize(self, hop: int):
+        self._set(self.P_HOP, hop)
+
+    def SetMix(self, mix: float):
+        self._set(self.P_MIX, mix)
+
+    def SetPhaseMode(self, mode: int):
+        self._set(self.P_PHASE_MODE, mode)
+
+    def SetFrozen(self, frozen: bool):
+        self._set(self.P_FROZEN, 1 if frozen else 0)
+
+    def Freeze(self):
+        self.SetFrozen(True)
+
+    def Unfreeze(self):
+        self.SetFrozen(False)
+
+    def HopSize(self) -> int:
+        return self.config().hop_size
+
+    def Mix(self) -> float:
+        return self.config().mix
+
+    def PhaseMode(self) -> int:
+        return self.config().phase_mode
+
+    def Frozen(self) -> bool:
+        return bool(self.config().frozen)
+
+    def state(self):
+        """(heldMagnitude [channels][N/2+1], phaseAcc [channels][N/2+1], hasFrozenFrame) of ad_specfreeze_state."""
+        bins = self.FrameSize() // 2 + 1
+        held, acc = np.zeros((self.channels, bins)), np.zeros((self.channels, bins))
+        has = C.c_int()
+        check(lib().ad_specfreeze_state(self._h, ptr(held), ptr(acc), C.byref(has)))
+        return held, acc, bool(has.value)
+
+    def norm(self, n: int) -> np.ndarray:
+        """The overlap-add norm (sum of w^2 in ascending frame order) of a call of n samples, by the device code."""
+        out = np.zeros(int(n))
+        check(lib().ad_specfreeze_norm(self._h, ptr(out), int(n)))
+        return out
+
+
+def pitchspec_resample_taps(analysis_hop: int, synthesis_hop: int, quality: int) -> np.ndarray:
+    """The prototype resample.Resample(x, analysisHop, synthesisHop, WithQuality(q))
+    designs (resample.go:153-187): the hops reduced by their gcd, the quality's profile."""
+    from . import resample as rs
+
+    g = rs._gcd(int(analysis_hop), int(synthesis_hop))
+    p = rs.QualityProfile(int(quality))
+    return rs.design_polyphase_fir(int(analysis_hop) // g, int(synthesis_hop) // g, p.TapsPerPhase, p.CutoffScale,
+                                   p.KaiserBeta)
+
+
+class SpectralPitchShifter(_StftHandle):
+    """pitch.SpectralPitchShifter (pitch_shift_spectral.go:36-646) for `channels`
+    instances sharing one configuration: NewSpectralPitchShifter(sample_rate)
+    with options as keywords (pitch_ratio, frame_size, analysis_hop,
+    window_type, resample_quality).  Stateless between calls.  The prototype
+    of the time stretch's resampling is designed here whenever the hops or the
+    quality change.  A rejected setter value raises and changes nothing."""
+
+    P_SAMPLE_RATE, P_RATIO, P_HOP, P_RESAMPLE_QUALITY = range(4)  # AD_PITCHSPEC_*
+    _kind = "pitchspec"
+    _config = PitchSpecConfig
+
+    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, **options):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        cfg = PitchSpecConfig()
+        lib().ad_pitchspec_default_config(C.byref(cfg), float(sample_rate))
+        for k, v in options.items():
+            if k in ("frame_size", "analysis_hop", "window_type", "resample_quality"):
+                setattr(cfg, k, int(v))
+            elif k == "pitch_ratio":
+                cfg.pitch_ratio = float(v)
+            else:
+                raise TypeError(f"unknown spectral pitch shifter option {k!r}")
+        w = spectral_window(cfg.window_type, max(cfg.frame_size, 0))
+        cfg.window = ptr(w)
+        check(lib().ad_pitchspec_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+        self._sync_taps()
+
+    def _sync_taps(self):
+        c = self.config()
+        hop, shop = c.analysis_hop, self.SynthesisHop()
+        if c.n_resample_taps == 0 and self.path() == 2 and shop != hop:
+            t = pitchspec_resample_taps(hop, shop, c.resample_quality)
+            check(lib().ad_pitchspec_set_resample_taps(self._h, ptr(t), t.size))
+
+    def _set(self, which: int, v):
+        super()._set(which, v)
+        self._sync_taps()
+
+    def SetFrameSize(self, size: int):
+        super().SetFrameSize(size)
+        self._sync_taps()
+
+    def SetPitchRatio(self, ratio: float):
+        self._set(self.P_RATIO, ratio)
+
+    def SetPitchSemitones(self, semitones: float):  # :164-177
+        s = float(semitones)
+        if not np.isfinite(s):
+            raise ErrInvalidArgument(AD_ERR_INVALID_ARGUMENT, f"spectral pitch shifter semitones must be finite: {s}")
+        self.SetPitchRatio(2.0 ** (s / 12.0))
+
+    def SetAnalysisHop(self, hop: int):
+        self._set(self.P_HOP, hop)
+
+    def SetResampleQuality(self, q: int):
+        self._set(self.P_RESAMPLE_QUALITY, q)
+
+    def PitchRatio(self) -> float:
+        return self.config().pitch_ratio
+
+    def PitchSemitones(self) -> float:  # :103
+        return 12.0 * float(np.log2(self.PitchRatio()))
+
+    def AnalysisHop(self) -> int:
+        return self.config().analysis_hop
+
+    def ResampleQuality(self) -> int:
+        return self.config().resample_quality
+
+    def EffectivePitchRatio(self) -> float:
+        r = C.c_double()
+        check(lib().ad_pitchspec_effective_ratio(self._h, C.byref(r)))
+        return r.value
+
+    def SynthesisHop(self) -> int:
+        h = C.c_int()
+        check(lib().ad_pitchspec_synthesis_hop(self._h, C.byref(h)))
+        return h.value
+
+    def path(self) -> int:
+        """0: the identity shortcut, 1: bin shifting, 2: time stretch (ad_pitchspec_path)."""
+        v = C.c_int()
+        check(lib().ad_pitchspec_path(self._h, C.byref(v)))
+        return v.value
 
 
 class EffectChain(_FxChain):

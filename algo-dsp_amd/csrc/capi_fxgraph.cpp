@@ -25,8 +25,9 @@
 //     the high band on a copy;
 //   * the reverbs other than Freeverb, the delays and the modulation effects
 //     (flanger, phaser, tremolo, ringmod) and the waveshapers (distortion,
-//     dist-cheb, bitcrusher), the de-esser and the transient shaper are ops
-//     of their own on their handles;
+//     dist-cheb, bitcrusher), the de-esser, the transient shaper, the spectral
+//     freeze and the spectral pitch shifter are ops of their own on their
+//     handles;
 //   * independent branches run concurrently on up to 8 streams (schedule()).
 #include <hip/hip_runtime.h>
 
@@ -110,10 +111,20 @@ struct TransientDel {
 };
 using TransientPtr = std::unique_ptr<ad_transient, TransientDel>;
 
+struct SpecfreezeDel {
+  void operator()(ad_specfreeze* f) const { ad_specfreeze_destroy(f); }
+};
+using SpecfreezePtr = std::unique_ptr<ad_specfreeze, SpecfreezeDel>;
+
+struct PitchspecDel {
+  void operator()(ad_pitchspec* f) const { ad_pitchspec_destroy(f); }
+};
+using PitchspecPtr = std::unique_ptr<ad_pitchspec, PitchspecDel>;
+
 struct FxOp {
   enum Kind {
     ZERO, COPY, MIX, CHAIN, CONV, FDN, DELAY, FLANGER, PHASER, TREMOLO, RINGMOD, DISTORTION, BITCRUSHER, DEESSER,
-    TRANSIENT
+    TRANSIENT, SPECFREEZE, PITCHSPEC
   } kind;
   int dst = -1;                 // buffer id (written; CHAIN and later kinds: read and written in place)
   std::vector<int> srcs;        // COPY / MIX: buffers read
@@ -129,6 +140,8 @@ struct FxOp {
   ad_bitcrusher* bitcrusher = nullptr;  // BITCRUSHER
   ad_deesser* deesser = nullptr;        // DEESSER
   ad_transient* transient = nullptr;    // TRANSIENT
+  ad_specfreeze* specfreeze = nullptr;  // SPECFREEZE
+  ad_pitchspec* pitchspec = nullptr;    // PITCHSPEC
   // schedule (see schedule()): lane 0 is the caller's stream
   int lane = 0;
   std::vector<int> waits;  // ops on other lanes this op waits for
@@ -165,6 +178,8 @@ struct ad_fx_graph {
   std::vector<BitcrusherPtr> bitcrushers;
   std::vector<DeesserPtr> deessers;
   std::vector<TransientPtr> transients;
+  std::vector<SpecfreezePtr> specfreezes;
+  std::vector<PitchspecPtr> pitchspecs;
   DevBuf<double> pool;   // buffers 1..nbuf-1, [nbuf-1][channels][cap]
   int64_t cap = 0;
   DevBuf<double> work;   // host-call staging
@@ -194,6 +209,8 @@ struct ad_fx_graph {
     bitcrushers.clear();
     deessers.clear();
     transients.clear();
+    specfreezes.clear();
+    pitchspecs.clear();
     if (stream) {
       (void)hipStreamSynchronize(stream);
       (void)lib_stream_destroy(stream);
@@ -245,7 +262,7 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
   int out_node = -1;
   for (int i = 0; i < n; ++i) {
     const ad_fx_node& d = nodes[i];
-    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_TRANSIENT || (d.type > AD_FXN_RINGMOD && d.type < AD_FXN_DISTORTION) ||
+    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_PITCHSPEC || (d.type > AD_FXN_RINGMOD && d.type < AD_FXN_DISTORTION) ||
         (d.type > AD_FXN_BITCRUSHER && d.type < AD_FXN_DEESSER))
       AD_FAIL(AD_ERR_UNKNOWN_EFFECT, "fx graph: node type not supported by the GPU runtime");
     if (d.type == AD_FXN_INPUT && i != 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: more than one input node");
@@ -298,6 +315,16 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
       const ad_transient_config* c = node_cfg<ad_transient_config>(cfg, i);
       if (!c || ad_transient_validate(c) != AD_OK)
         AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: transient shaper node without a valid config of its size");
+    }
+    if (d.type == AD_FXN_SPECFREEZE) {
+      const ad_specfreeze_config* c = node_cfg<ad_specfreeze_config>(cfg, i);
+      if (!c || ad_specfreeze_validate(c) != AD_OK)
+        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: spectral freeze node without a valid config of its size");
+    }
+    if (d.type == AD_FXN_PITCHSPEC) {
+      const ad_pitchspec_config* c = node_cfg<ad_pitchspec_config>(cfg, i);
+      if (!c || ad_pitchspec_validate(c) != AD_OK)
+        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: spectral pitch shifter node without a valid config of its size");
     }
     if (d.type == AD_FXN_COMPRESSOR && (d.dyn_mode < 0 || d.dyn_mode > 2))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: bad dynamics mode");
@@ -471,6 +498,28 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
       g->ops.push_back(op);
       continue;
     }
+    if (d.type == AD_FXN_SPECFREEZE) {
+      flush(g, gr);
+      ad_specfreeze* sf = nullptr;
+      ck(ad_specfreeze_create(node_cfg<ad_specfreeze_config>(cfg, i), g->channels, g->device, &sf));
+      g->specfreezes.emplace_back(sf);
+      FxOp op{FxOp::SPECFREEZE};
+      op.dst = b;
+      op.specfreeze = sf;
+      g->ops.push_back(op);
+      continue;
+    }
+    if (d.type == AD_FXN_PITCHSPEC) {
+      flush(g, gr);
+      ad_pitchspec* ps = nullptr;
+      ck(ad_pitchspec_create(node_cfg<ad_pitchspec_config>(cfg, i), g->channels, g->device, &ps));
+      g->pitchspecs.emplace_back(ps);
+      FxOp op{FxOp::PITCHSPEC};
+      op.dst = b;
+      op.pitchspec = ps;
+      g->ops.push_back(op);
+      continue;
+    }
     const int lvl = d.type == AD_FXN_BIQUAD ? 1 : (d.type == AD_FXN_COMPRESSOR ? 2 : 3);
     if (gr.open && (lvl < gr.level() || (lvl == gr.level() && lvl > 1))) flush(g, gr);
     gr.open = true;
@@ -634,6 +683,12 @@ void run(ad_fx_graph* g, double* d0, int64_t stride0, int64_t n, hipStream_t s) 
       case FxOp::TRANSIENT:
         ck(ad_transient_process_device(op.transient, dst, st(op.dst), n, ls));
         break;
+      case FxOp::SPECFREEZE:
+        ck(ad_specfreeze_process_device(op.specfreeze, dst, st(op.dst), n, ls));
+        break;
+      case FxOp::PITCHSPEC:
+        ck(ad_pitchspec_process_device(op.pitchspec, dst, st(op.dst), n, ls));
+        break;
     }
     if (op.signal) AD_HIP(hipEventRecord(g->op_ev[i], ls));
   }
@@ -730,6 +785,8 @@ int ad_fx_graph_reset(ad_fx_graph* g) {
     for (auto& f : g->bitcrushers) ck(ad_bitcrusher_reset(f.get()));
     for (auto& f : g->deessers) ck(ad_deesser_reset(f.get()));
     for (auto& f : g->transients) ck(ad_transient_reset(f.get()));
+    for (auto& f : g->specfreezes) ck(ad_specfreeze_reset(f.get()));
+    for (auto& f : g->pitchspecs) ck(ad_pitchspec_reset(f.get()));
   });
 }
 

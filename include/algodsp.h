@@ -559,7 +559,11 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
  *   AD_FXN_DEESSER     dynamics.DeEsser.ProcessInPlace (dyn-deesser,
  *                      runtime_dynamics.go:240-314) and
  *   AD_FXN_TRANSIENT   dynamics.TransientShaper.ProcessInPlace (dyn-transient,
- *                      runtime_dynamics.go:316-351), configured through
+ *                      runtime_dynamics.go:316-351),
+ *   AD_FXN_SPECFREEZE  effects.SpectralFreeze.ProcessInPlace (spectral-freeze,
+ *                      runtime_filter_pitch_reverb.go:274-303) and
+ *   AD_FXN_PITCHSPEC   pitch.SpectralPitchShifter.ProcessInPlace (pitch-spectral,
+ *                      runtime_filter_pitch_reverb.go:248-272), configured through
  *                      ad_fx_graph_create_cfg.
  * The result is the output node's buffer.  Linear runs of in-place nodes fuse
  * into one launch (bit-identical, see capi_fxgraph.cpp).  Other node types
@@ -588,6 +592,10 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
 /* 17 is not assigned: it stays AD_ERR_UNKNOWN_EFFECT */
 #define AD_FXN_DEESSER 18   /* dyn-deesser: an ad_deesser created from cfg[i], an op of its own */
 #define AD_FXN_TRANSIENT 19 /* dyn-transient: an ad_transient created from cfg[i], an op of its own */
+#define AD_FXN_SPECFREEZE 20 /* spectral-freeze: an ad_specfreeze created from cfg[i] (its window table is read
+                                at create), an op of its own */
+#define AD_FXN_PITCHSPEC 21  /* pitch-spectral: an ad_pitchspec created from cfg[i] (its window and resampling
+                                prototype are read at create), an op of its own */
 #define AD_FX_MAX_PARENTS 8
 struct ad_fdn_config;
 struct ad_delay_config;
@@ -1203,6 +1211,104 @@ int ad_deesser_process(ad_deesser* d, double* buf, int64_t n);
 int ad_deesser_process_device(ad_deesser* d, double* d_buf, int64_t stride, int64_t n, void* stream);
 int ad_deesser_reset(ad_deesser* d);
 void ad_deesser_destroy(ad_deesser* d);
+
+/* ---- effects.SpectralFreeze, pitch.SpectralPitchShifter (dsp/effects/
+ * spectral_freeze.go, dsp/effects/pitch/pitch_shift_spectral.go) ---------------
+ * Short-frame STFT overlap-add for `channels` instances that share one
+ * configuration; buf [channels][n] (host) / [channels][stride] (device), in
+ * place, one call = one Process of the whole buffer.  Frame sizes are powers of
+ * two in [64, 4096]; a larger power of two, which the reference would accept,
+ * is AD_ERR_INVALID_ARGUMENT (a documented limit).
+ *
+ * The window is a table of frame_size coefficients the caller computes
+ * (window.Generate(t, N, WithPeriodic())); window_type only names it.  The
+ * table is copied by create / set_frame / set_window; get_config returns NULL
+ * pointers.  A stated deviation: the imaginary parts of analysis bins 0 and
+ * N/2 are set to +0.0 before the polar conversion.
+ *
+ * ad_specfreeze: set_param follows the reference's setters (a rejected value
+ * changes nothing); AD_SPECFREEZE_FROZEN clears the captured frame when the
+ * value changes (SetFrozen :169-175); set_frame is SetFrameSize :115-127 with
+ * the window for the new size (pulls a hop >= frame down to frame / 4, rebuilds
+ * the state); set_window is SetWindowType :152-155 (rebuilds the state); reset
+ * is Reset :184-189.  ad_specfreeze_state copies heldMagnitude and phaseAcc
+ * [channels][frame_size / 2 + 1] and hasFrozenFrame.  ad_specfreeze_norm
+ * writes the overlap-add norm of a call of n samples (host, [n]).
+ *
+ * ad_pitchspec: the reference's Process with its identity shortcut
+ * (|ratio - 1| <= 1e-9 leaves the buffer), the bin-shift path for
+ * |ratio - 1| <= 0.15 and the time stretch with resample.Resample(stretched,
+ * analysisHop, synthesisHop, quality) and fitLength beyond.  The resampling
+ * prototype is the caller's (designPolyphaseFIR for the reduced hops and the
+ * quality's profile): resample_taps [n_resample_taps], a multiple of the
+ * reduced analysis hop; a stretch call without one is AD_ERR_INVALID_ARGUMENT.
+ * set_param(AD_PITCHSPEC_RATIO / HOP) and set_frame drop the prototype when
+ * they change the reduced hops; ad_pitchspec_set_resample_taps installs one.  */
+/* ad_*_profile(h, enable, ms): with ms, the milliseconds spent in each pass (events around the launches) by
+ * the calls made since profiling was switched on, ms[AD_STFT_PASSES]; then profiling on or off. */
+#define AD_STFT_PASS_ANALYSIS 0  /* window, forward transform, hypot / atan2 */
+#define AD_STFT_PASS_WALK 1      /* the serial walk over frames */
+#define AD_STFT_PASS_SYNTHESIS 2 /* sincos, inverse transform, window */
+#define AD_STFT_PASS_OLA 3       /* overlap-add gather, norm, mix */
+#define AD_STFT_PASS_RESAMPLE 4  /* the time stretch's resampling and fitLength */
+#define AD_STFT_PASS_FUSED 5     /* analysis and synthesis in one kernel (the unfrozen freeze) */
+#define AD_STFT_PASSES 6
+typedef struct ad_specfreeze ad_specfreeze;
+typedef struct ad_specfreeze_config {
+  double sample_rate, mix;
+  int frame_size, hop_size, phase_mode, frozen, window_type;
+  const double* window; /* [frame_size] */
+} ad_specfreeze_config;
+#define AD_SPECFREEZE_PHASE_HOLD 0
+#define AD_SPECFREEZE_PHASE_ADVANCE 1
+#define AD_SPECFREEZE_SAMPLE_RATE 0 /* SetSampleRate spectral_freeze.go:104 */
+#define AD_SPECFREEZE_HOP 1         /* SetHopSize :130 */
+#define AD_SPECFREEZE_MIX 2         /* SetMix :141 */
+#define AD_SPECFREEZE_PHASE_MODE 3  /* SetPhaseMode :158 */
+#define AD_SPECFREEZE_FROZEN 4      /* SetFrozen :169 */
+void ad_specfreeze_default_config(ad_specfreeze_config* cfg, double sample_rate);
+int ad_specfreeze_validate(const ad_specfreeze_config* cfg);
+int ad_specfreeze_create(const ad_specfreeze_config* cfg, int channels, int device, ad_specfreeze** out);
+int ad_specfreeze_set_param(ad_specfreeze* f, int which, double value);
+int ad_specfreeze_set_frame(ad_specfreeze* f, int frame_size, const double* window);
+int ad_specfreeze_set_window(ad_specfreeze* f, int window_type, const double* window);
+int ad_specfreeze_get_config(const ad_specfreeze* f, ad_specfreeze_config* cfg);
+int ad_specfreeze_state(ad_specfreeze* f, double* held_magnitude, double* phase_acc, int* has_frozen);
+int ad_specfreeze_norm(ad_specfreeze* f, double* norm, int64_t n);
+int ad_specfreeze_process(ad_specfreeze* f, double* buf, int64_t n);
+int ad_specfreeze_process_device(ad_specfreeze* f, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_specfreeze_reset(ad_specfreeze* f);
+int ad_specfreeze_profile(ad_specfreeze* f, int enable, double* ms);
+void ad_specfreeze_destroy(ad_specfreeze* f);
+
+typedef struct ad_pitchspec ad_pitchspec;
+typedef struct ad_pitchspec_config {
+  double sample_rate, pitch_ratio;
+  int frame_size, analysis_hop, window_type, resample_quality;
+  const double* window;        /* [frame_size] */
+  const double* resample_taps; /* [n_resample_taps], or NULL */
+  int64_t n_resample_taps;
+} ad_pitchspec_config;
+#define AD_PITCHSPEC_SAMPLE_RATE 0      /* SetSampleRate pitch_shift_spectral.go:140 */
+#define AD_PITCHSPEC_RATIO 1            /* SetPitchRatio :151 */
+#define AD_PITCHSPEC_HOP 2              /* SetAnalysisHop :199 */
+#define AD_PITCHSPEC_RESAMPLE_QUALITY 3 /* SetResampleQuality :217 */
+void ad_pitchspec_default_config(ad_pitchspec_config* cfg, double sample_rate);
+int ad_pitchspec_validate(const ad_pitchspec_config* cfg);
+int ad_pitchspec_create(const ad_pitchspec_config* cfg, int channels, int device, ad_pitchspec** out);
+int ad_pitchspec_set_param(ad_pitchspec* p, int which, double value);
+int ad_pitchspec_set_frame(ad_pitchspec* p, int frame_size, const double* window);
+int ad_pitchspec_set_window(ad_pitchspec* p, int window_type, const double* window);
+int ad_pitchspec_set_resample_taps(ad_pitchspec* p, const double* taps, int64_t n_taps);
+int ad_pitchspec_get_config(const ad_pitchspec* p, ad_pitchspec_config* cfg);
+int ad_pitchspec_effective_ratio(const ad_pitchspec* p, double* ratio); /* EffectivePitchRatio :108-114 */
+int ad_pitchspec_synthesis_hop(const ad_pitchspec* p, int* hop);        /* SynthesisHop :123-129 */
+int ad_pitchspec_path(const ad_pitchspec* p, int* path);                /* 0 identity, 1 bin shift, 2 time stretch */
+int ad_pitchspec_process(ad_pitchspec* p, double* buf, int64_t n);
+int ad_pitchspec_process_device(ad_pitchspec* p, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_pitchspec_reset(ad_pitchspec* p);
+int ad_pitchspec_profile(ad_pitchspec* p, int enable, double* ms);
+void ad_pitchspec_destroy(ad_pitchspec* p);
 
 /* ---- spectral correlation / deconvolution (dsp/conv/correlate.go,
  * dsp/conv/deconvolve.go) --------------------------------------
