@@ -408,6 +408,33 @@ def _declare(L: C.CDLL) -> None:
         "ad_deesser_metrics": (C.c_int, [vp, C.c_int, c_double_p, c_double_p]),
         "ad_deesser_reset_metrics": (C.c_int, [vp]),
         "ad_deesser_gain": (C.c_int, [vp, c_double_p, c_double_p, i64]),
+        "ad_fx_chain_reset_compressor_metrics": (C.c_int, [vp]),
+        "ad_xover_validate": (C.c_int, [c_double_p, C.c_int, C.c_int, C.c_double]),
+        "ad_xover_sections": (C.c_int, [c_double_p, C.c_int, C.c_int, C.c_double, c_double_p, i64,
+                                        C.POINTER(C.c_int)]),
+        "ad_xover_create": (C.c_int, [c_double_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]),
+        "ad_xover_process": (C.c_int, [vp, c_double_p, c_double_p, i64]),
+        "ad_xover_process_device": (C.c_int, [vp, vp, i64, vp, i64, i64, i64, vp]),
+        "ad_xover_get_state": (C.c_int, [vp, C.c_int, c_double_p, i64]),
+        "ad_xover_set_state": (C.c_int, [vp, C.c_int, c_double_p, i64]),
+        "ad_xover_reset": (C.c_int, [vp]),
+        "ad_xover_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
+        "ad_xover_set_pipelined": (C.c_int, [vp, C.c_int]),
+        "ad_xover_destroy": (None, [vp]),
+        "ad_multiband_validate": (C.c_int, [c_double_p, C.c_int, C.c_int, C.c_double]),
+        "ad_multiband_create": (C.c_int, [c_double_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(vp)]),
+        "ad_multiband_set_band": (C.c_int, [vp, C.c_int, C.POINTER(CompressorConfig)]),
+        "ad_multiband_get_band": (C.c_int, [vp, C.c_int, C.POINTER(CompressorConfig)]),
+        "ad_multiband_process": (C.c_int, [vp, c_double_p, i64]),
+        "ad_multiband_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
+        "ad_multiband_process_multi": (C.c_int, [vp, c_double_p, c_double_p, i64]),
+        "ad_multiband_process_multi_device": (C.c_int, [vp, vp, i64, vp, i64, i64, i64, vp]),
+        "ad_multiband_metrics": (C.c_int, [vp, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
+        "ad_multiband_reset_metrics": (C.c_int, [vp]),
+        "ad_multiband_reset": (C.c_int, [vp]),
+        "ad_multiband_xover_state": (C.c_int, [vp, C.c_int, c_double_p, i64]),
+        "ad_multiband_set_chunk": (C.c_int, [vp, i64]),
+        "ad_multiband_destroy": (None, [vp]),
         "ad_specfreeze_state": (C.c_int, [vp, c_double_p, c_double_p, C.POINTER(C.c_int)]),
         "ad_specfreeze_norm": (C.c_int, [vp, c_double_p, i64]),
         "ad_pitchspec_set_resample_taps": (C.c_int, [vp, c_double_p, i64]),

@@ -16,6 +16,8 @@ like the reference's own tests:
   effects.BitCrusher             dsp/effects/bit_crusher.go
   dynamics.TransientShaper       dsp/effects/dynamics/transient_shaper.go
   dynamics.DeEsser               dsp/effects/dynamics/deesser.go
+  crossover.MultiBand            dsp/filter/crossover/crossover.go
+  dynamics.MultibandCompressor   dsp/effects/dynamics/multiband.go
   effects.SpectralFreeze         dsp/effects/spectral_freeze.go
   pitch.SpectralPitchShifter     dsp/effects/pitch/pitch_shift_spectral.go
   fir.Filter                     dsp/filter/fir/filter.go
@@ -1200,6 +1202,287 @@ class DeEsser(_DynHandle):
         out = np.empty_like(lv)
         check(lib().ad_deesser_gain(self._h, ptr(lv), ptr(out), int(lv.size)))
         return out.reshape(np.shape(levels))
+
+
+def _freq_args(freqs):
+    f = f64(list(freqs)).reshape(-1)
+    return f, ptr(f), int(f.size)
+
+
+def crossover_sections(freqs, order: int, sample_rate: float) -> np.ndarray:
+    """The sections an ad_xover runs, [len(freqs)][2 (LP, HP)][S][5] {b0, b1, b2, a1, a2} (ad_xover_sections);
+    host only."""
+    f, fp, nf = _freq_args(freqs)
+    s = C.c_int()
+    check(lib().ad_xover_sections(fp, nf, int(order), float(sample_rate), None, 0, C.byref(s)))
+    tab = np.zeros((nf, 2, s.value, 5))
+    check(lib().ad_xover_sections(fp, nf, int(order), float(sample_rate), ptr(tab), int(tab.size), C.byref(s)))
+    return tab
+
+
+class MultiBandCrossover(_Handle):
+    """crossover.MultiBand (dsp/filter/crossover/crossover.go:113-222) on `channels` lanes: len(freqs) cascaded
+    two-way Linkwitz-Riley stages of one order, len(freqs) + 1 bands, every band bit for bit the reference's."""
+
+    _kind = "xover"
+
+    def __init__(self, freqs, order: int, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        f, fp, nf = _freq_args(freqs)
+        check(lib().ad_xover_create(fp, nf, int(order), float(sample_rate), self.channels, int(device),
+                                    C.byref(self._h)))
+        self._freqs, self._order, self._fs = f.copy(), int(order), float(sample_rate)
+        self._sections = crossover_sections(f, order, sample_rate)
+
+    def NumBands(self) -> int:  # :163
+        return int(self._freqs.size) + 1
+
+    def sections(self) -> np.ndarray:
+        """[stages][2 (LP, HP)][S][5] {b0, b1, b2, a1, a2}: the sections in use."""
+        return self._sections.copy()
+
+    def ProcessBlock(self, x) -> np.ndarray:  # :194-215 -> [bands][channels][n]
+        b = _as2d(np.ascontiguousarray(x, dtype=np.float64), self.channels)
+        out = np.zeros((self.NumBands(), self.channels, b.shape[1]))
+        check(lib().ad_xover_process(self._h, ptr(b), ptr(out), b.shape[1]))
+        return out
+
+    def ProcessInPlace(self, buf):
+        raise TypeError("a crossover has no in-place form: use ProcessBlock")
+
+    def process_device(self, d_in: int, in_stride: int, d_bands: int, row_stride: int, band_stride: int, n: int,
+                       stream: int | None = None):
+        check(lib().ad_xover_process_device(self._h, C.c_void_p(d_in), int(in_stride), C.c_void_p(d_bands),
+                                            int(row_stride), int(band_stride), int(n), C.c_void_p(stream or 0)))
+
+    def get_state(self, channel: int = 0) -> np.ndarray:
+        """[stages][2][S][2] {s0, s1} of `channel`."""
+        st = np.zeros(self._sections.shape[:3] + (2,))
+        check(lib().ad_xover_get_state(self._h, int(channel), ptr(st), int(st.size)))
+        return st
+
+    def set_state(self, channel: int, state):
+        st = f64(state).reshape(self._sections.shape[:3] + (2,))
+        check(lib().ad_xover_set_state(self._h, int(channel), ptr(st), int(st.size)))
+
+    def kernel_info(self):
+        """(waves per workgroup, samples per tile, lds_bytes) of ad_xover_kernel_info."""
+        v = [C.c_int() for _ in range(3)]
+        check(lib().ad_xover_kernel_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def set_pipelined(self, on: bool):
+        """All stages in one launch as a pipeline over time tiles (True, the default), or one stage per launch;
+        the same bits either way."""
+        check(lib().ad_xover_set_pipelined(self._h, int(bool(on))))
+
+
+class BandView:
+    """Read-only view of one band's compressor (MultibandCompressor.Band): the reference's getters."""
+
+    _GETTERS = {"Threshold": "threshold_db", "Ratio": "ratio", "Knee": "knee_db", "Attack": "attack_ms",
+                "Release": "release_ms", "MakeupGain": "makeup_db", "RMSWindow": "rms_window_ms",
+                "SidechainLowCut": "sidechain_low_cut_hz", "SidechainHighCut": "sidechain_high_cut_hz",
+                "Topology": "topology", "DetectorMode": "detector_mode", "SampleRate": "sample_rate"}
+
+    def __init__(self, cfg: CompressorConfig):
+        object.__setattr__(self, "_cfg", cfg)
+
+    def __getattr__(self, name):
+        if name in BandView._GETTERS:
+            return lambda: getattr(self._cfg, BandView._GETTERS[name])
+        if name == "AutoMakeup":
+            return lambda: bool(self._cfg.auto_makeup)
+        if name == "FeedbackRatioScale":
+            return lambda: bool(self._cfg.feedback_ratio_scale)
+        return getattr(self._cfg, name)  # the config's own field names
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a band view is read-only: use the MultibandCompressor setters")
+
+
+# BandConfig fields (multiband.go:27-41) in applyBandConfig's order -> (setter, keep value)
+_BAND_CONFIG = (("ThresholdDB", "SetBandThreshold", None), ("Ratio", "SetBandRatio", 0), ("KneeDB", "SetBandKnee", None),
+                ("AttackMs", "SetBandAttack", 0), ("ReleaseMs", "SetBandRelease", 0),
+                ("MakeupGainDB", "SetBandMakeupGain", None), ("AutoMakeup", "SetBandAutoMakeup", None),
+                ("Topology", "SetBandTopology", None), ("DetectorMode", "SetBandDetectorMode", None),
+                ("FeedbackRatioScale", "SetBandFeedbackRatioScale", None), ("RMSWindowMs", "SetBandRMSWindow", None),
+                ("SidechainLowCutHz", "SetBandSidechainLowCut", None),
+                ("SidechainHighCutHz", "SetBandSidechainHighCut", None))
+
+
+class MultibandCompressor(_Handle):
+    """dynamics.MultibandCompressor (dsp/effects/dynamics/multiband.go) on `channels` lanes: the crossover, one
+    compressor per band, the bands summed in band order.  `configs`: one BandConfig-like dict per band
+    (NewMultibandCompressorWithConfig :130-150); a key left out, None, or 0 for Ratio / AttackMs / ReleaseMs
+    keeps the default."""
+
+    _kind = "multiband"
+
+    def __init__(self, freqs, order: int, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE,
+                 configs=None):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        f, fp, nf = _freq_args(freqs)
+        if configs is not None and len(configs) != nf + 1:  # :131-135
+            raise ErrInvalidArgument(AD_ERR_INVALID_ARGUMENT, f"expected {nf + 1} band configs, got {len(configs)}")
+        check(lib().ad_multiband_create(fp, nf, int(order), float(sample_rate), self.channels, int(device),
+                                        C.byref(self._h)))
+        self._freqs, self._order, self._fs = f.copy(), int(order), float(sample_rate)
+        for i, cfg in enumerate(configs or ()):
+            self.SetBandConfig(i, cfg)
+
+    def NumBands(self) -> int:  # :153-155
+        return int(self._freqs.size) + 1
+
+    def CrossoverFreqs(self) -> list:  # :158-163
+        return [float(v) for v in self._freqs]
+
+    def CrossoverOrder(self) -> int:  # :166-168
+        return self._order
+
+    def SampleRate(self) -> float:  # :171-173
+        return self._fs
+
+    def _band(self, band: int) -> CompressorConfig:
+        cfg = CompressorConfig()
+        check(lib().ad_multiband_get_band(self._h, int(band), C.byref(cfg)))
+        return cfg
+
+    def Band(self, i: int) -> BandView:  # :178-180
+        return BandView(self._band(i))
+
+    def _set(self, band: int, **kv):
+        cfg = self._band(band)  # a bad band index raises here, checkBand :555-561
+        for k, v in kv.items():
+            setattr(cfg, k, v)
+        check(lib().ad_multiband_set_band(self._h, int(band), C.byref(cfg)))  # rejected: nothing changes
+
+    # per-band setters :190-329
+    def SetBandThreshold(self, band, db):
+        self._set(band, threshold_db=float(db))
+
+    def SetBandRatio(self, band, ratio):
+        self._set(band, ratio=float(ratio))
+
+    def SetBandKnee(self, band, db):
+        self._set(band, knee_db=float(db))
+
+    def SetBandAttack(self, band, ms):
+        self._set(band, attack_ms=float(ms))
+
+    def SetBandRelease(self, band, ms):
+        self._set(band, release_ms=float(ms))
+
+    def SetBandMakeupGain(self, band, db):  # :242-249: turns auto makeup off
+        self._set(band, makeup_db=float(db), auto_makeup=0)
+
+    def SetBandAutoMakeup(self, band, on):
+        self._set(band, auto_makeup=int(bool(on)))
+
+    def SetBandTopology(self, band, topology):
+        self._set(band, topology=int(topology))
+
+    def SetBandDetectorMode(self, band, mode):
+        self._set(band, detector_mode=int(mode))
+
+    def SetBandFeedbackRatioScale(self, band, on):
+        self._set(band, feedback_ratio_scale=int(bool(on)))
+
+    def SetBandRMSWindow(self, band, ms):
+        self._set(band, rms_window_ms=float(ms))
+
+    def SetBandSidechainLowCut(self, band, hz):
+        self._set(band, sidechain_low_cut_hz=float(hz))
+
+    def SetBandSidechainHighCut(self, band, hz):
+        self._set(band, sidechain_high_cut_hz=float(hz))
+
+    def SetBandConfig(self, band, cfg):  # :322-329, applyBandConfig :563-658: stops at the first rejected field
+        self._band(band)
+        unknown = set(cfg) - {k for k, _, _ in _BAND_CONFIG}
+        if unknown:
+            raise KeyError(f"unknown BandConfig field(s): {sorted(unknown)}")
+        for key, setter, keep in _BAND_CONFIG:
+            v = cfg.get(key)
+            if v is None or (keep is not None and v == keep):
+                continue
+            getattr(self, setter)(band, v)
+
+    def _all(self, setter, v):  # :331-437: stops at the first band that rejects; earlier bands stay changed
+        for b in range(self.NumBands()):
+            getattr(self, setter)(b, v)
+
+    def SetAllBandsThreshold(self, db):
+        self._all("SetBandThreshold", db)
+
+    def SetAllBandsRatio(self, ratio):
+        self._all("SetBandRatio", ratio)
+
+    def SetAllBandsKnee(self, db):
+        self._all("SetBandKnee", db)
+
+    def SetAllBandsAttack(self, ms):
+        self._all("SetBandAttack", ms)
+
+    def SetAllBandsRelease(self, ms):
+        self._all("SetBandRelease", ms)
+
+    def SetAllBandsTopology(self, topology):
+        self._all("SetBandTopology", topology)
+
+    def SetAllBandsDetectorMode(self, mode):
+        self._all("SetBandDetectorMode", mode)
+
+    def SetAllBandsFeedbackRatioScale(self, on):
+        self._all("SetBandFeedbackRatioScale", on)
+
+    def SetAllBandsRMSWindow(self, ms):
+        self._all("SetBandRMSWindow", ms)
+
+    def ProcessInPlaceMulti(self, x) -> np.ndarray:  # :507-523 -> [bands][channels][n]; x is not written
+        b = _as2d(np.ascontiguousarray(x, dtype=np.float64), self.channels)
+        out = np.zeros((self.NumBands(), self.channels, b.shape[1]))
+        check(lib().ad_multiband_process_multi(self._h, ptr(b), ptr(out), b.shape[1]))
+        return out
+
+    def ProcessStereoInPlace(self, left, right):  # :493-502 on a handle of two channels, one per side
+        if self.channels != 2:
+            raise ValueError("ProcessStereoInPlace needs a processor of two channels")
+        if len(left) != len(right):
+            raise ValueError(f"stereo buffers must have equal length, got {len(left)} and {len(right)}")
+        both = np.stack([f64(left), f64(right)])
+        self.ProcessInPlace(both)
+        left[:], right[:] = both[0], both[1]
+
+    def process_multi_device(self, d_in: int, in_stride: int, d_bands: int, row_stride: int, band_stride: int, n: int,
+                             stream: int | None = None):
+        check(lib().ad_multiband_process_multi_device(self._h, C.c_void_p(d_in), int(in_stride), C.c_void_p(d_bands),
+                                                      int(row_stride), int(band_stride), int(n),
+                                                      C.c_void_p(stream or 0)))
+
+    def GetMetrics(self, channel: int = 0) -> list:  # :537-544 -> per band (InputPeak, OutputPeak, GainReduction)
+        out = []
+        for b in range(self.NumBands()):
+            v = [C.c_double() for _ in range(3)]
+            check(lib().ad_multiband_metrics(self._h, b, int(channel), *[C.byref(x) for x in v]))
+            out.append(tuple(x.value for x in v))
+        return out
+
+    def ResetMetrics(self):  # :547-551
+        check(lib().ad_multiband_reset_metrics(self._h))
+
+    def xover_state(self, channel: int = 0) -> np.ndarray:
+        """The crossover's [stages][2][S][2] {s0, s1} of `channel`."""
+        s = crossover_sections(self._freqs, self._order, self._fs).shape
+        st = np.zeros(s[:3] + (2,))
+        check(lib().ad_multiband_xover_state(self._h, int(channel), ptr(st), int(st.size)))
+        return st
+
+    def SetChunk(self, samples: int):
+        """Runs every call in passes of at most `samples` samples (0: as many as the scratch cap allows)."""
+        check(lib().ad_multiband_set_chunk(self._h, int(samples)))
 
 
 # window.Type (dsp/window/window.go:12-16) of the windows the STFT processors take

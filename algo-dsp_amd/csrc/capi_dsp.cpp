@@ -1098,6 +1098,21 @@ int ad_fx_chain_compressor_metrics(ad_fx_chain* h, int channel, double* input_pe
   });
 }
 
+int ad_fx_chain_reset_compressor_metrics(ad_fx_chain* h) {
+  return fx_guard(h, [&] {
+    if (!h->comp_on) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "compressor stage not configured");
+    fx_quiesce(h);
+    std::vector<CompChState> st(h->channels);
+    AD_HIP(hipMemcpy(st.data(), h->cs.p, st.size() * sizeof(CompChState), hipMemcpyDeviceToHost));
+    for (auto& s : st) {  // CompressorMetrics{GainReduction: 1.0}
+      s.in_peak = 0.0;
+      s.out_peak = 0.0;
+      s.gr = 1.0;
+    }
+    AD_HIP(hipMemcpy(h->cs.p, st.data(), st.size() * sizeof(CompChState), hipMemcpyHostToDevice));
+  });
+}
+
 int ad_fx_chain_eq_state(ad_fx_chain* h, double* state, int64_t cap) {
   return fx_guard(h, [&] {
     const int64_t need = (int64_t)h->channels * h->nsec * 2;

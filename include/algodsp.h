@@ -468,6 +468,9 @@ int ad_fx_chain_process_device(ad_fx_chain* h, double* d_buf, int64_t stride, in
  * input peak, output peak, minimum gain (gain reduction, linear). */
 int ad_fx_chain_compressor_metrics(ad_fx_chain* h, int channel, double* input_peak, double* output_peak,
                                    double* gain_reduction);
+/* Compressor.ResetMetrics (compressor.go:389-391) of every channel: the peaks
+ * to 0, the gain reduction to 1; the dynamics state is not touched. */
+int ad_fx_chain_reset_compressor_metrics(ad_fx_chain* h);
 /* EQ section state [channels][nsec][2] {d0, d1} (Chain.State, chain.go:122-130). */
 int ad_fx_chain_eq_state(ad_fx_chain* h, double* state, int64_t cap);
 /* Chain.SetState (chain.go:130-138) / Section.SetState (section.go:152-155)
@@ -1211,6 +1214,90 @@ int ad_deesser_process(ad_deesser* d, double* buf, int64_t n);
 int ad_deesser_process_device(ad_deesser* d, double* d_buf, int64_t stride, int64_t n, void* stream);
 int ad_deesser_reset(ad_deesser* d);
 void ad_deesser_destroy(ad_deesser* d);
+
+/* ---- crossover.MultiBand, dynamics.MultibandCompressor (dsp/filter/crossover/
+ * crossover.go:113-222, dsp/effects/dynamics/multiband.go) ----------------------
+ * For `channels` instances sharing one configuration.
+ *
+ * ad_xover: nfreq cascaded two-way Linkwitz-Riley stages, nfreq + 1 bands; the
+ * highpass of a stage is the next stage's input (ProcessBlock :194-215).  Every
+ * band is bit for bit the reference's: the sections run biquad.Section.
+ * ProcessSample's recurrence, first-order sections included, with no FMA.
+ * validate: crossover.New :32-43 and NewMultiBand :135-144 -- order positive
+ *   and even, every frequency in (0, fs/2), strictly ascending -- and the
+ *   kernel's limits, order <= 24 and nfreq <= 7 (maxMultibandOrder and
+ *   maxMultibandBands - 1 of multiband.go:15-16).  Host only.
+ * sections: host only.  The sections in use, [nfreq][2 (LP, HP)][S][5]
+ *   {b0, b1, b2, a1, a2}, designed with the operations of pass.LinkwitzRileyLP /
+ *   HP / HPInverted in their order, and S, the sections per side (the halved-
+ *   order Butterworth prototype twice: 2, 2, 4, 4, 12 for orders 2, 4, 6, 8,
+ *   24).  `sections` may be NULL to ask for S alone; cap counts doubles.
+ * process: host in [channels][n], bands [nfreq + 1][channels][n].
+ * process_device: band b of channel c starts at d_bands + b * band_stride +
+ *   c * row_stride; in_stride, row_stride >= n, band_stride >= (channels - 1) *
+ *   row_stride + n; d_in must not overlap the bands.  Calls of any length
+ *   continue the stream.
+ * get_state / set_state: one channel's [nfreq][2][S][2] {s0, s1}, the
+ *   checkpoint surface (as ad_fx_chain_eq_state); cap and n count doubles.
+ * kernel_info: waves per workgroup (one per stage in the pipelined form, 1 in
+ *   the one-stage-per-launch form), samples per tile, LDS bytes of a workgroup.
+ * set_pipelined: 1 (default) runs all stages in one launch as a pipeline over
+ *   time tiles; 0 runs one stage per launch.  The two give the same bits.      */
+typedef struct ad_xover ad_xover;
+int ad_xover_validate(const double* freqs, int nfreq, int order, double sample_rate);
+int ad_xover_sections(const double* freqs, int nfreq, int order, double sample_rate, double* sections, int64_t cap,
+                      int* sections_per_side);
+int ad_xover_create(const double* freqs, int nfreq, int order, double sample_rate, int channels, int device,
+                    ad_xover** out);
+int ad_xover_process(ad_xover* x, const double* in, double* bands, int64_t n);
+int ad_xover_process_device(ad_xover* x, const double* d_in, int64_t in_stride, double* d_bands, int64_t row_stride,
+                            int64_t band_stride, int64_t n, void* stream);
+int ad_xover_get_state(ad_xover* x, int channel, double* state, int64_t cap);
+int ad_xover_set_state(ad_xover* x, int channel, const double* state, int64_t n);
+int ad_xover_reset(ad_xover* x);
+int ad_xover_kernel_info(const ad_xover* x, int* waves_per_workgroup, int* tile, int* lds_bytes);
+int ad_xover_set_pipelined(ad_xover* x, int on);
+void ad_xover_destroy(ad_xover* x);
+
+/* ad_multiband: the crossover, one dynamics.Compressor per band, the bands
+ * summed in band order (ProcessInPlace :468-489).  The crossover is bit for
+ * bit the reference's; each band's compressor is the ad_fx_chain compressor
+ * stage with its bars.
+ * validate: validateMultibandParams :661-709 -- at least one frequency, at
+ *   most 8 bands, order even in [2, 24], every frequency finite, >= 20 Hz,
+ *   < Nyquist, ascending.  Host only.
+ * create: every band starts from ad_compressor_default_config.
+ * set_band: ad_compressor_validate's rules; cfg->sample_rate must be the
+ *   handle's.  A rejected config or band index changes nothing.  The band's
+ *   state carries on as ad_fx_chain_set_compressor documents.
+ * process / process_device: in place on [channels][n] / [channels][stride].
+ * process_multi / process_multi_device: per-band outputs laid out as
+ *   ad_xover_process / _process_device do; the input is not written
+ *   (ProcessInPlaceMulti :507-523).
+ * metrics: GetMetrics :537-544 of one band and channel; reset_metrics :547-551.
+ * reset: :528-534, the crossover and every compressor.
+ * xover_state: as ad_xover_get_state.
+ * set_chunk: a call runs in passes of at most `samples` samples with every
+ *   state carried; 0 (default): as many as keep the band planes of a pass
+ *   within 2 GiB.                                                              */
+typedef struct ad_multiband ad_multiband;
+int ad_multiband_validate(const double* freqs, int nfreq, int order, double sample_rate);
+int ad_multiband_create(const double* freqs, int nfreq, int order, double sample_rate, int channels, int device,
+                        ad_multiband** out);
+int ad_multiband_set_band(ad_multiband* m, int band, const ad_compressor_config* cfg);
+int ad_multiband_get_band(const ad_multiband* m, int band, ad_compressor_config* cfg);
+int ad_multiband_process(ad_multiband* m, double* buf, int64_t n);
+int ad_multiband_process_device(ad_multiband* m, double* d_buf, int64_t stride, int64_t n, void* stream);
+int ad_multiband_process_multi(ad_multiband* m, const double* in, double* bands, int64_t n);
+int ad_multiband_process_multi_device(ad_multiband* m, const double* d_in, int64_t in_stride, double* d_bands,
+                                      int64_t row_stride, int64_t band_stride, int64_t n, void* stream);
+int ad_multiband_metrics(ad_multiband* m, int band, int channel, double* input_peak, double* output_peak,
+                         double* gain_reduction);
+int ad_multiband_reset_metrics(ad_multiband* m);
+int ad_multiband_reset(ad_multiband* m);
+int ad_multiband_xover_state(ad_multiband* m, int channel, double* state, int64_t cap);
+int ad_multiband_set_chunk(ad_multiband* m, int64_t samples);
+void ad_multiband_destroy(ad_multiband* m);
 
 /* ---- effects.SpectralFreeze, pitch.SpectralPitchShifter (dsp/effects/
  * spectral_freeze.go, dsp/effects/pitch/pitch_shift_spectral.go) ---------------
