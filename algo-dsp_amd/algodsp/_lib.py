@@ -173,6 +173,36 @@ class DeEsserConfig(C.Structure):
                [(n, C.c_int) for n in ("mode", "detector", "listen", "filter_order")]
 
 
+class VocoderConfig(C.Structure):
+    """ad_vocoder_config (include/algodsp.h); field k is parameter AD_VOCODER_* = k where the reference has a
+    setter."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "synth_q", "attack_ms", "release_ms", "input_level",
+                                          "synth_level", "vocoder_level")] + \
+               [(n, C.c_int) for n in ("downsample", "layout", "synth_q_set")]
+
+
+VOCODER_MAX_BANDS = 32  # AD_VOCODER_MAX_BANDS
+
+
+class VocoderTables(C.Structure):
+    """ad_vocoder_tables (include/algodsp.h): what the reference caches for a config."""
+
+    _fields_ = [("num_bands", C.c_int), ("num_groups", C.c_int), ("downsample_max", C.c_int),
+                ("factors", C.c_int * VOCODER_MAX_BANDS), ("group_of_band", C.c_int * VOCODER_MAX_BANDS),
+                ("group_factors", C.c_int * VOCODER_MAX_BANDS)] + \
+               [(n, (C.c_double * 5) * VOCODER_MAX_BANDS) for n in ("analysis", "synthesis", "decimated",
+                                                                    "antialias")] + \
+               [("attack_coeff", C.c_double), ("release_coeff", C.c_double),
+                ("ds_attack", C.c_double * VOCODER_MAX_BANDS), ("ds_release", C.c_double * VOCODER_MAX_BANDS)]
+
+
+class LookaheadConfig(C.Structure):
+    """ad_lookahead_config (include/algodsp.h); field k is parameter AD_LOOKAHEAD_* = k."""
+
+    _fields_ = [(n, C.c_double) for n in ("sample_rate", "threshold_db", "release_ms", "lookahead_ms")]
+
+
 class SpecFreezeConfig(C.Structure):
     """ad_specfreeze_config (include/algodsp.h); window points at frame_size coefficients."""
 
@@ -409,6 +439,33 @@ def _declare(L: C.CDLL) -> None:
         "ad_deesser_reset_metrics": (C.c_int, [vp]),
         "ad_deesser_gain": (C.c_int, [vp, c_double_p, c_double_p, i64]),
         "ad_fx_chain_reset_compressor_metrics": (C.c_int, [vp]),
+        "ad_lookahead_default_config": (None, [C.POINTER(LookaheadConfig), C.c_double]),
+        "ad_lookahead_validate": (C.c_int, [C.POINTER(LookaheadConfig)]),
+        "ad_lookahead_derived": (C.c_int, [C.POINTER(LookaheadConfig), c_double_p, c_double_p, c_double_p, c_int64_p]),
+        "ad_lookahead_create": (C.c_int, [C.POINTER(LookaheadConfig), C.c_int, C.c_int, C.POINTER(vp)]),
+        "ad_lookahead_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
+        "ad_lookahead_get_config": (C.c_int, [vp, C.POINTER(LookaheadConfig)]),
+        "ad_lookahead_get_state": (C.c_int, [vp, C.c_int, c_double_p]),
+        "ad_lookahead_gain": (C.c_int, [vp, c_double_p, c_double_p, i64]),
+        "ad_lookahead_last_envelope": (C.c_int, [vp, c_double_p, i64]),
+        "ad_lookahead_process": (C.c_int, [vp, c_double_p, c_double_p, i64, i64]),
+        "ad_lookahead_process_device": (C.c_int, [vp, vp, i64, vp, i64, i64, i64, vp]),
+        "ad_lookahead_reset": (C.c_int, [vp]),
+        "ad_lookahead_destroy": (None, [vp]),
+        "ad_vocoder_default_config": (None, [C.POINTER(VocoderConfig), C.c_double]),
+        "ad_vocoder_validate": (C.c_int, [C.POINTER(VocoderConfig)]),
+        "ad_vocoder_derived": (C.c_int, [C.POINTER(VocoderConfig), C.POINTER(VocoderTables)]),
+        "ad_vocoder_create": (C.c_int, [C.POINTER(VocoderConfig), C.c_int, C.c_int, C.POINTER(vp)]),
+        "ad_vocoder_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
+        "ad_vocoder_get_config": (C.c_int, [vp, C.POINTER(VocoderConfig)]),
+        "ad_vocoder_num_bands": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "ad_vocoder_downsample_factors": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+        "ad_vocoder_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
+        "ad_vocoder_get_state": (C.c_int, [vp, C.c_int, c_double_p, C.POINTER(C.c_int)]),
+        "ad_vocoder_process": (C.c_int, [vp, c_double_p, c_double_p, c_double_p, i64]),
+        "ad_vocoder_process_device": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, i64, vp]),
+        "ad_vocoder_reset": (C.c_int, [vp]),
+        "ad_vocoder_destroy": (None, [vp]),
         "ad_xover_validate": (C.c_int, [c_double_p, C.c_int, C.c_int, C.c_double]),
         "ad_xover_sections": (C.c_int, [c_double_p, C.c_int, C.c_int, C.c_double, c_double_p, i64,
                                         C.POINTER(C.c_int)]),

@@ -23,7 +23,10 @@ ad_fx_graph_create_ext); _Node keeps its layout.  The distortion, dist-cheb
 and bitcrusher nodes carry theirs as (structure, size) in a second parallel
 array (FxNodeCfg, ad_fx_graph_create_cfg), and so do dyn-deesser,
 dyn-transient, spectral-freeze and pitch-spectral (whose structures point at the
-Hann table and the resampling prototype computed here).
+Hann table and the resampling prototype computed here).  With
+Chain(sidechain=True) the dyn-lookahead and vocoder nodes run as well: their
+structures (ad_fx_lookahead_node, ad_fx_vocoder_node) carry the effect's config
+and the side parents, the edges with toPortIndex 1.
 """
 from __future__ import annotations
 
@@ -35,8 +38,8 @@ import numpy as np
 
 from . import design
 from ._lib import (BitCrusherConfig, CompressorConfig, DeEsserConfig, DelayConfig, DistortionConfig, FdnConfig,
-                   FlangerConfig, FxNodeCfg, PhaserConfig, PitchSpecConfig, RingModConfig, SpecFreezeConfig,
-                   TransientConfig, TremoloConfig, check, lib, ptr)
+                   FlangerConfig, FxNodeCfg, LookaheadConfig, PhaserConfig, PitchSpecConfig, RingModConfig,
+                   SpecFreezeConfig, TransientConfig, TremoloConfig, VocoderConfig, check, lib, ptr)
 from .processors import section_table
 
 INPUT_NODE_ID = "_input"  # graph.go:10-13
@@ -50,6 +53,8 @@ FXN_PHASER, FXN_TREMOLO, FXN_RINGMOD = 11, 12, 13
 FXN_DISTORTION, FXN_BITCRUSHER = 15, 16  # 14 is not assigned
 FXN_DEESSER, FXN_TRANSIENT = 18, 19  # 17 is not assigned
 FXN_SPECFREEZE, FXN_PITCHSPEC = 20, 21
+FXN_LOOKAHEAD, FXN_VOCODER = 23, 24  # 22 is not assigned
+SIDECHAIN_TYPES = ("dyn-lookahead", "vocoder")  # splitMainAndSideParents chain_process.go:128
 MAX_PARENTS = 8
 
 FILTER_TYPES = ("filter", "filter-lowpass", "filter-highpass", "filter-bandpass", "filter-notch",
@@ -81,6 +86,16 @@ class _NodeExt(C.Structure):
 
     _fields_ = [("phaser", C.POINTER(PhaserConfig)), ("tremolo", C.POINTER(TremoloConfig)),
                 ("ringmod", C.POINTER(RingModConfig))]
+
+
+def _side_node(config_type):
+    """ad_fx_lookahead_node / ad_fx_vocoder_node: the effect's config, then the side parents."""
+
+    class _SideNode(C.Structure):
+        _fields_ = [("config", config_type), ("n_side", C.c_int), ("side_parents", C.c_int * MAX_PARENTS),
+                    ("side_ports", C.c_int * MAX_PARENTS)]
+
+    return _SideNode
 
 
 def clamp(v, lo, hi):  # core.Clamp
@@ -495,6 +510,29 @@ def spectral_pitch_params(p: Params, fs: float):
     return c, w, taps
 
 
+def lookahead_params(p: Params, fs: float) -> LookaheadConfig:
+    """lookaheadLimiterRuntime.Configure (runtime_dynamics.go:94-116) on NewLookaheadLimiter(fs)."""
+    cfg = LookaheadConfig()
+    lib().ad_lookahead_default_config(C.byref(cfg), fs)
+    cfg.threshold_db = clamp(p.GetNum("thresholdDB", -1), -24, 0)
+    cfg.release_ms = clamp(p.GetNum("releaseMs", 100), 1, 5000)
+    cfg.lookahead_ms = clamp(p.GetNum("lookaheadMs", 3), 0, 200)
+    return cfg
+
+
+def vocoder_params(p: Params, fs: float) -> VocoderConfig:
+    """vocoderRuntime.Configure (runtime_misc.go:74-106) on NewVocoder(fs): the node has no layout, band-count
+    or downsampling parameter."""
+    cfg = VocoderConfig()
+    lib().ad_vocoder_default_config(C.byref(cfg), fs)
+    cfg.attack_ms = clamp(p.GetNum("attackMs", 0.5), 0.01, 100)
+    cfg.release_ms = clamp(p.GetNum("releaseMs", 2.0), 0.01, 1000)
+    cfg.input_level = clamp(p.GetNum("inputLevel", 0), 0, 10)
+    cfg.synth_level = clamp(p.GetNum("synthLevel", 0), 0, 10)
+    cfg.vocoder_level = clamp(p.GetNum("vocoderLevel", 1), 0, 10)
+    return cfg
+
+
 def _config_dict(cfg) -> dict:
     """A config structure's fields as plain data (arrays as lists)."""
     return {f: (list(getattr(cfg, f)) if isinstance(getattr(cfg, f), C.Array) else getattr(cfg, f))
@@ -575,11 +613,16 @@ def conv_reverb_kernel(p: Params, provider):
 class Chain:
     """effectchain.Chain for `channels` independent channels of one graph.
     `ir_provider` is effectchain.WithIRProvider's IRProvider (GetIR(index) ->
-    (samples [ch][n], sample_rate, ok)) for reverb-conv nodes."""
+    (samples [ch][n], sample_rate, ok)) for reverb-conv nodes.  `sidechain=True`
+    admits the dyn-lookahead and vocoder nodes and routes their toPortIndex 1
+    edges to the side input; the default keeps both types UnknownEffect."""
 
     def __init__(self, sample_rate: float = 48000.0, channels: int = 1, designer=None, device: int = 0,
-                 ir_provider=None):
+                 ir_provider=None, sidechain: bool = False):
         self.sample_rate = float(sample_rate)
+        # the dyn-lookahead and vocoder nodes, with their side inputs, run on the GPU only where the caller asks:
+        # a caller that takes UnknownEffect as "run this graph on the reference" keeps getting it for them
+        self.sidechain = bool(sidechain)
         self.channels = int(channels)
         self.designer = designer
         self.ir_provider = ir_provider
@@ -617,10 +660,16 @@ class Chain:
         for i, k in enumerate(order):
             p = g.Nodes[k]
             d = nodes[i]
-            # mainParents (splitMainAndSideParents, chain_process.go:120-134): the
-            # GPU runtime has no sidechain node types, so every edge is a main edge
-            par = [(idx[e[0]], e[2]) for e in g.Incoming[k]]
-            if len(par) > MAX_PARENTS:
+            # splitMainAndSideParents (chain_process.go:124-144): on a dyn-lookahead or vocoder node the edges
+            # with toPortIndex 1 are side parents (Chain(sidechain=True); without it the two types stay
+            # UnknownEffect); on every other node toPortIndex is ignored.  The rule is
+            # applied afresh to the parsed edge list, where the reference filters g.Incoming[id] in place and
+            # loses a side edge listed before a main edge from the second block on.
+            sidechain = self.sidechain and p.Type in SIDECHAIN_TYPES
+            par = [(idx[e[0]], e[2]) for e in g.Incoming[k] if not (sidechain and e[3] == 1)]
+            side = [(idx[e[0]], 1 if g.Nodes[e[0]].Type == NODE_TYPE_SPLIT_FREQ and e[2] == 1 else 0)
+                    for e in g.Incoming[k] if sidechain and e[3] == 1]
+            if len(par) > MAX_PARENTS or len(side) > MAX_PARENTS:
                 raise UnknownEffect(f"node {k}: more than {MAX_PARENTS} parents")
             if par:
                 pa = (C.c_int32 * len(par))(*[q[0] for q in par])
@@ -776,6 +825,21 @@ class Chain:
                 cfgs[i].config, cfgs[i].bytes = C.addressof(cfg), C.sizeof(cfg)
                 sd.update(type="pitchspec", pitchspec={f: getattr(cfg, f) for f, _ in cfg._fields_
                                                        if f not in ("window", "resample_taps")})
+            elif sidechain:
+                lookahead = t == "dyn-lookahead"
+                d.type = FXN_LOOKAHEAD if lookahead else FXN_VOCODER
+                cfg = lookahead_params(p, fs) if lookahead else vocoder_params(p, fs)
+                check((lib().ad_lookahead_validate if lookahead else lib().ad_vocoder_validate)(C.byref(cfg)))
+                node = _side_node(type(cfg))()
+                node.config = cfg
+                node.n_side = len(side)
+                for j, (sp, sport) in enumerate(side):
+                    node.side_parents[j], node.side_ports[j] = sp, sport
+                keep.append(node)
+                cfgs[i].config, cfgs[i].bytes = C.addressof(node), C.sizeof(node)
+                name = "lookahead" if lookahead else "vocoder"
+                sd.update(type=name, side_parents=list(side))
+                sd[name] = _config_dict(cfg)
             elif t in ("reverb-freeverb", "reverb"):  # reverbRuntime without model "fdn" is Freeverb
                 d.type = FXN_FREEVERB
                 for j, v in enumerate(freeverb_params(p)):

@@ -16,6 +16,8 @@ like the reference's own tests:
   effects.BitCrusher             dsp/effects/bit_crusher.go
   dynamics.TransientShaper       dsp/effects/dynamics/transient_shaper.go
   dynamics.DeEsser               dsp/effects/dynamics/deesser.go
+  effects.Vocoder                dsp/effects/vocoder.go
+  dynamics.LookaheadLimiter      dsp/effects/dynamics/lookahead_limiter.go
   crossover.MultiBand            dsp/filter/crossover/crossover.go
   dynamics.MultibandCompressor   dsp/effects/dynamics/multiband.go
   effects.SpectralFreeze         dsp/effects/spectral_freeze.go
@@ -34,8 +36,9 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (AD_ERR_INVALID_ARGUMENT, BitCrusherConfig, CompressorConfig, DeEsserConfig, DelayConfig,
-                   DistortionConfig, ErrInvalidArgument, FdnConfig, FlangerConfig, PhaserConfig, PitchSpecConfig,
-                   RingModConfig, SpecFreezeConfig, TransientConfig, TremoloConfig, check, f64, lib, ptr)
+                   DistortionConfig, ErrInvalidArgument, FdnConfig, FlangerConfig, LookaheadConfig, PhaserConfig,
+                   PitchSpecConfig, RingModConfig, SpecFreezeConfig, TransientConfig, TremoloConfig, VocoderConfig,
+                   VocoderTables, check, f64, lib, ptr)
 
 DEVICE = 0
 SEC_STRIDE = 6  # {pre_gain, b0, b1, b2, a1, a2}
@@ -1202,6 +1205,299 @@ class DeEsser(_DynHandle):
         out = np.empty_like(lv)
         check(lib().ad_deesser_gain(self._h, ptr(lv), ptr(out), int(lv.size)))
         return out.reshape(np.shape(levels))
+
+
+def _rows(t, channels: int):
+    """(device pointer, row stride, n) of device rows [channels][stride]: anything with torch's data_ptr(),
+    stride() and shape."""
+    if t.dim() != 2 or t.shape[0] != channels or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"device rows must be [{channels}][n] with unit sample stride")
+    if t.element_size() != 8 or not t.is_floating_point():
+        raise TypeError("device rows must be float64")
+    n = int(t.shape[1])
+    return t.data_ptr(), max(int(t.stride(0)), n) if channels == 1 else int(t.stride(0)), n  # one row: any stride
+
+
+def vocoder_derived(cfg: VocoderConfig) -> dict:
+    """What the reference caches for a config, of ad_vocoder_derived: host only.  dict(num_bands, factors,
+    group_factors, group_of_band, downsample_max, analysis, synthesis, decimated [bands][5], antialias
+    [groups][5], attack_coeff, release_coeff, ds_attack, ds_release [bands]); sections are {b0, b1, b2, a1, a2}."""
+    t = VocoderTables()
+    check(lib().ad_vocoder_derived(C.byref(cfg), C.byref(t)))
+    nb, ng = t.num_bands, t.num_groups
+    sec = lambda a, n: np.array([list(a[i]) for i in range(n)], dtype=np.float64).reshape(n, 5)  # noqa: E731
+    on = ng > 0
+    return dict(num_bands=nb, downsample_max=t.downsample_max, factors=list(t.factors[:nb]) if on else None,
+                group_factors=list(t.group_factors[:ng]), group_of_band=list(t.group_of_band[:nb]) if on else None,
+                analysis=sec(t.analysis, nb), synthesis=sec(t.synthesis, nb), decimated=sec(t.decimated, nb if on else 0),
+                antialias=sec(t.antialias, ng), attack_coeff=t.attack_coeff, release_coeff=t.release_coeff,
+                ds_attack=np.array(t.ds_attack[:nb if on else 0]), ds_release=np.array(t.ds_release[:nb if on else 0]))
+
+
+class Vocoder(_Handle):
+    """effects.Vocoder (vocoder.go:199-833) for `channels` instances sharing one
+    configuration: NewVocoder(sample_rate, options...) with the options as
+    keywords (layout, synth_q, attack_ms, release_ms, input_level, synth_level,
+    vocoder_level, downsample), or `config` (a VocoderConfig) applied whole.
+    synth_q given as a keyword is WithVocoderSynthesisQ: it overrides Bark's
+    per-band default too.  Each channel has its own modulator row, carrier row
+    and state.  A rejected value raises ErrInvalidArgument and changes nothing."""
+
+    (P_SAMPLE_RATE, _P_SYNTH_Q, P_ATTACK, P_RELEASE, P_INPUT_LEVEL, P_SYNTH_LEVEL, P_VOCODER_LEVEL,
+     P_DOWNSAMPLING) = range(8)  # AD_VOCODER_*
+    THIRD_OCTAVE, BARK = 0, 1  # BandLayout :15-25
+    _kind = "vocoder"
+    _options = ("synth_q", "attack_ms", "release_ms", "input_level", "synth_level", "vocoder_level")
+
+    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        cfg = VocoderConfig()
+        if config is None:
+            lib().ad_vocoder_default_config(C.byref(cfg), float(sample_rate))
+        else:
+            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        for k, v in options.items():
+            if k == "layout":
+                cfg.layout = int(v)
+            elif k == "downsample":
+                cfg.downsample = 1 if v else 0
+            elif k in self._options:
+                setattr(cfg, k, float(v))
+                if k == "synth_q":
+                    cfg.synth_q_set = 1
+            else:
+                raise TypeError(f"unknown vocoder option {k!r}")
+        check(lib().ad_vocoder_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+
+    def _set(self, which: int, v):
+        check(lib().ad_vocoder_set_param(self._h, which, float(v)))
+
+    def config(self) -> VocoderConfig:
+        cfg = VocoderConfig()
+        check(lib().ad_vocoder_get_config(self._h, C.byref(cfg)))
+        return cfg
+
+    def SetSampleRate(self, v):  # :673-683
+        self._set(self.P_SAMPLE_RATE, v)
+
+    def SetAttack(self, v):  # :772-783
+        self._set(self.P_ATTACK, v)
+
+    def SetRelease(self, v):  # :786-797
+        self._set(self.P_RELEASE, v)
+
+    def SetInputLevel(self, v):  # :800-809
+        self._set(self.P_INPUT_LEVEL, v)
+
+    def SetSynthLevel(self, v):  # :812-821
+        self._set(self.P_SYNTH_LEVEL, v)
+
+    def SetVocoderLevel(self, v):  # :824-833
+        self._set(self.P_VOCODER_LEVEL, v)
+
+    def SetDownsampling(self, on: bool):  # :737-769
+        self._set(self.P_DOWNSAMPLING, 1 if on else 0)
+
+    def SampleRate(self) -> float:  # :688-717
+        return self.config().sample_rate
+
+    def Layout(self) -> int:
+        return self.config().layout
+
+    def NumBands(self) -> int:
+        n = C.c_int()
+        check(lib().ad_vocoder_num_bands(self._h, C.byref(n)))
+        return n.value
+
+    def SynthesisQ(self) -> float:
+        return self.config().synth_q
+
+    def Attack(self) -> float:
+        return self.config().attack_ms
+
+    def Release(self) -> float:
+        return self.config().release_ms
+
+    def InputLevel(self) -> float:
+        return self.config().input_level
+
+    def SynthLevel(self) -> float:
+        return self.config().synth_level
+
+    def VocoderLevel(self) -> float:
+        return self.config().vocoder_level
+
+    def Downsampling(self) -> bool:
+        return bool(self.config().downsample)
+
+    def DownsampleFactors(self):  # :722-731: None with downsampling off
+        f, n = (C.c_int * 32)(), C.c_int()
+        check(lib().ad_vocoder_downsample_factors(self._h, f, 32, C.byref(n)))
+        return list(f[:n.value]) if n.value else None
+
+    def derived(self) -> dict:
+        return vocoder_derived(self.config())
+
+    def kernel_info(self):
+        """(lanes per channel, samples per chunk, lds_bytes of a workgroup) of ad_vocoder_kernel_info."""
+        v = [C.c_int() for _ in range(3)]
+        check(lib().ad_vocoder_kernel_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def get_state(self, channel: int = 0):
+        """(state [9][32], downsampleCount) of `channel`: rows {analysis s0, s1, synthesis s0, s1, decimated s0,
+        s1, envelope} by band, then the anti-alias {s0, s1} by group."""
+        st, cnt = np.zeros((9, 32)), C.c_int()
+        check(lib().ad_vocoder_get_state(self._h, int(channel), ptr(st), C.byref(cnt)))
+        return st, cnt.value
+
+    def ProcessBlock(self, modulator, carrier) -> np.ndarray:  # :634-645 on host rows [channels][n]
+        m = _as2d(np.ascontiguousarray(modulator, dtype=np.float64), self.channels)
+        c = _as2d(np.ascontiguousarray(carrier, dtype=np.float64), self.channels)
+        if m.shape != c.shape:
+            raise ErrInvalidArgument(AD_ERR_INVALID_ARGUMENT, "vocoder: buffer length mismatch")
+        out = np.empty_like(m)
+        check(lib().ad_vocoder_process(self._h, ptr(m), ptr(c), ptr(out), m.shape[1]))
+        return out.reshape(np.shape(modulator))
+
+    def ProcessInPlace(self, buf):
+        raise TypeError("a vocoder takes a modulator and a carrier: use ProcessBlock or process")
+
+    def process(self, modulator, carrier, out=None, stream: int | None = None):
+        """ProcessBlock on device rows [channels][stride] (torch tensors, or anything with their data_ptr(),
+        stride() and shape), asynchronous on `stream`.  `out` may be the modulator or the carrier; None: the
+        modulator, as the graph's node runs.  Returns out."""
+        out = modulator if out is None else out
+        (mp, ms, n), (cp, cs, cn), (op, os_, on) = (_rows(t, self.channels) for t in (modulator, carrier, out))
+        if n != cn or n != on:  # :635-638
+            raise ErrInvalidArgument(AD_ERR_INVALID_ARGUMENT, "vocoder: buffer length mismatch")
+        self.process_device(mp, ms, cp, cs, op, os_, n, stream)
+        return out
+
+    def process_device(self, d_mod: int, mod_stride: int, d_car: int, car_stride: int, d_out: int, out_stride: int,
+                       n: int, stream: int | None = None):
+        check(lib().ad_vocoder_process_device(self._h, C.c_void_p(d_mod), int(mod_stride), C.c_void_p(d_car),
+                                              int(car_stride), C.c_void_p(d_out), int(out_stride), int(n),
+                                              C.c_void_p(stream or 0)))
+
+
+def lookahead_derived(cfg: LookaheadConfig) -> dict:
+    """dict(attack_coeff, release_coeff, threshold_log2, delay_samples) for a config, of ad_lookahead_derived:
+    what the limiter's Compressor core caches and the delay D, host only."""
+    a, r, th, d = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+    check(lib().ad_lookahead_derived(C.byref(cfg), C.byref(a), C.byref(r), C.byref(th), C.byref(d)))
+    return dict(attack_coeff=a.value, release_coeff=r.value, threshold_log2=th.value, delay_samples=d.value)
+
+
+class LookaheadLimiter(_Handle):
+    """dynamics.LookaheadLimiter (lookahead_limiter.go:23-239) for `channels`
+    instances sharing one configuration: NewLookaheadLimiter(sample_rate) with
+    options as keywords (threshold_db, release_ms, lookahead_ms), or `config`
+    (a LookaheadConfig) applied whole.  A rejected setter value raises
+    ErrInvalidArgument and changes nothing."""
+
+    P_SAMPLE_RATE, P_THRESHOLD, P_RELEASE, P_LOOKAHEAD = range(4)  # AD_LOOKAHEAD_*
+    _kind = "lookahead"
+    _options = ("threshold_db", "release_ms", "lookahead_ms")
+
+    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
+        self.channels = int(channels)
+        self._h = C.c_void_p()
+        cfg = LookaheadConfig()
+        if config is None:
+            lib().ad_lookahead_default_config(C.byref(cfg), float(sample_rate))
+        else:
+            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        for k, v in options.items():
+            if k not in self._options:
+                raise TypeError(f"unknown lookahead limiter option {k!r}")
+            setattr(cfg, k, float(v))
+        check(lib().ad_lookahead_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+
+    def _set(self, which: int, v):
+        check(lib().ad_lookahead_set_param(self._h, which, float(v)))
+
+    def config(self) -> LookaheadConfig:
+        cfg = LookaheadConfig()
+        check(lib().ad_lookahead_get_config(self._h, C.byref(cfg)))
+        return cfg
+
+    def SetSampleRate(self, v):  # :146-161
+        self._set(self.P_SAMPLE_RATE, v)
+
+    def SetThreshold(self, v):  # :99-113
+        self._set(self.P_THRESHOLD, v)
+
+    def SetRelease(self, v):  # :116-130
+        self._set(self.P_RELEASE, v)
+
+    def SetLookahead(self, v):  # :133-143
+        self._set(self.P_LOOKAHEAD, v)
+
+    def SampleRate(self) -> float:  # :164-173
+        return self.config().sample_rate
+
+    def Threshold(self) -> float:
+        return self.config().threshold_db
+
+    def Release(self) -> float:
+        return self.config().release_ms
+
+    def Lookahead(self) -> float:
+        return self.config().lookahead_ms
+
+    def derived(self) -> dict:
+        return lookahead_derived(self.config())
+
+    def DelaySamples(self) -> int:
+        return self.derived()["delay_samples"]
+
+    def get_state(self, channel: int = 0) -> float:
+        """The detector envelope of `channel`."""
+        e = C.c_double()
+        check(lib().ad_lookahead_get_state(self._h, int(channel), C.byref(e)))
+        return e.value
+
+    def gain(self, levels):
+        """GainForLevel(level) by the device code a call runs.  Nothing advances."""
+        lv = f64(levels).reshape(-1)
+        out = np.empty_like(lv)
+        check(lib().ad_lookahead_gain(self._h, ptr(lv), ptr(out), int(lv.size)))
+        return out.reshape(np.shape(levels))
+
+    def last_envelope(self, n: int) -> np.ndarray:
+        """The detector envelope of every sample of the last call, [channels][n]."""
+        out = np.zeros((self.channels, int(n)))
+        check(lib().ad_lookahead_last_envelope(self._h, ptr(out), int(n)))
+        return out
+
+    def ProcessInPlace(self, buf):  # :213-217
+        self.ProcessInPlaceSidechain(buf, None)
+
+    def ProcessInPlaceSidechain(self, program, sidechain):  # :221-230 on host rows; a short sidechain reads as 0
+        b = _as2d(program, self.channels)
+        if sidechain is None:
+            check(lib().ad_lookahead_process(self._h, ptr(b), None, 0, b.shape[1]))
+            return
+        s = _as2d(np.ascontiguousarray(sidechain, dtype=np.float64), self.channels)
+        sp = ptr(s) if s.size else ptr(np.zeros(1))  # an empty sidechain is still a sidechain: all zeros
+        check(lib().ad_lookahead_process(self._h, ptr(b), sp, s.shape[1], b.shape[1]))
+
+    def process(self, program, sidechain=None, stream: int | None = None):
+        """ProcessInPlace / ProcessInPlaceSidechain on device rows [channels][stride] (torch tensors, or anything
+        with their data_ptr(), stride() and shape), asynchronous on `stream`.  Returns program."""
+        pp, ps, n = _rows(program, self.channels)
+        sp, ss, sn = (0, 0, 0) if sidechain is None else _rows(sidechain, self.channels)
+        if sidechain is not None and sn == 0:
+            sp, ss = pp, 0  # an empty sidechain is still a sidechain, all zeros: any address, never read
+        self.process_device(pp, ps, n, stream, sp, ss, sn)
+        return program
+
+    def process_device(self, d_buf: int, stride: int, n: int, stream: int | None = None, d_side: int = 0,
+                       side_stride: int = 0, side_n: int = 0):
+        check(lib().ad_lookahead_process_device(self._h, C.c_void_p(d_buf), int(stride), C.c_void_p(d_side or None),
+                                                int(side_stride), int(side_n), int(n), C.c_void_p(stream or 0)))
 
 
 def _freq_args(freqs):

@@ -28,6 +28,12 @@
 //     dist-cheb, bitcrusher), the de-esser, the transient shaper, the spectral
 //     freeze and the spectral pitch shifter are ops of their own on their
 //     handles;
+//   * the lookahead limiter and the vocoder are ops that rewrite the node's
+//     buffer in place and read a second, side buffer (op.srcs): the mix of the
+//     node's side parents.  A side consumer counts among a parent's consumers,
+//     so the parent's buffer is not handed to a main consumer that would
+//     rewrite it, and schedule() orders the side read after its producer and
+//     any later writer of that buffer after the read, across lanes;
 //   * independent branches run concurrently on up to 8 streams (schedule()).
 #include <hip/hip_runtime.h>
 
@@ -121,13 +127,23 @@ struct PitchspecDel {
 };
 using PitchspecPtr = std::unique_ptr<ad_pitchspec, PitchspecDel>;
 
+struct LookaheadDel {
+  void operator()(ad_lookahead* f) const { ad_lookahead_destroy(f); }
+};
+using LookaheadPtr = std::unique_ptr<ad_lookahead, LookaheadDel>;
+
+struct VocoderDel {
+  void operator()(ad_vocoder* f) const { ad_vocoder_destroy(f); }
+};
+using VocoderPtr = std::unique_ptr<ad_vocoder, VocoderDel>;
+
 struct FxOp {
   enum Kind {
     ZERO, COPY, MIX, CHAIN, CONV, FDN, DELAY, FLANGER, PHASER, TREMOLO, RINGMOD, DISTORTION, BITCRUSHER, DEESSER,
-    TRANSIENT, SPECFREEZE, PITCHSPEC
+    TRANSIENT, SPECFREEZE, PITCHSPEC, LOOKAHEAD, VOCODER
   } kind;
   int dst = -1;                 // buffer id (written; CHAIN and later kinds: read and written in place)
-  std::vector<int> srcs;        // COPY / MIX: buffers read
+  std::vector<int> srcs;        // COPY / MIX: buffers read; LOOKAHEAD / VOCODER: the side buffer, if any (read only)
   ad_fx_chain* chain = nullptr;   // CHAIN
   ad_conv* conv = nullptr;        // CONV (many-channel convolution reverb)
   ad_fdn* fdn = nullptr;          // FDN (many-channel FDN reverb)
@@ -142,6 +158,8 @@ struct FxOp {
   ad_transient* transient = nullptr;    // TRANSIENT
   ad_specfreeze* specfreeze = nullptr;  // SPECFREEZE
   ad_pitchspec* pitchspec = nullptr;    // PITCHSPEC
+  ad_lookahead* lookahead = nullptr;    // LOOKAHEAD
+  ad_vocoder* vocoder = nullptr;        // VOCODER
   // schedule (see schedule()): lane 0 is the caller's stream
   int lane = 0;
   std::vector<int> waits;  // ops on other lanes this op waits for
@@ -180,6 +198,8 @@ struct ad_fx_graph {
   std::vector<TransientPtr> transients;
   std::vector<SpecfreezePtr> specfreezes;
   std::vector<PitchspecPtr> pitchspecs;
+  std::vector<LookaheadPtr> lookaheads;
+  std::vector<VocoderPtr> vocoders;
   DevBuf<double> pool;   // buffers 1..nbuf-1, [nbuf-1][channels][cap]
   int64_t cap = 0;
   DevBuf<double> work;   // host-call staging
@@ -211,6 +231,8 @@ struct ad_fx_graph {
     transients.clear();
     specfreezes.clear();
     pitchspecs.clear();
+    lookaheads.clear();
+    vocoders.clear();
     if (stream) {
       (void)hipStreamSynchronize(stream);
       (void)lib_stream_destroy(stream);
@@ -255,6 +277,24 @@ const Cfg* node_cfg(const ad_fx_node_cfg* cfg, int i) {
   return static_cast<const Cfg*>(cfg[i].config);
 }
 
+// The side parents of node i (the edges with toPortIndex 1 of a dyn-lookahead or vocoder node), or none.
+struct Side {
+  int n = 0;
+  const int* parents = nullptr;
+  const int* ports = nullptr;
+};
+Side side_of(const ad_fx_node* nodes, const ad_fx_node_cfg* cfg, int i) {
+  Side s;
+  if (nodes[i].type == AD_FXN_LOOKAHEAD) {
+    const ad_fx_lookahead_node* c = node_cfg<ad_fx_lookahead_node>(cfg, i);
+    if (c) s = Side{c->n_side, c->side_parents, c->side_ports};
+  } else if (nodes[i].type == AD_FXN_VOCODER) {
+    const ad_fx_vocoder_node* c = node_cfg<ad_fx_vocoder_node>(cfg, i);
+    if (c) s = Side{c->n_side, c->side_parents, c->side_ports};
+  }
+  return s;
+}
+
 void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext, const ad_fx_node_cfg* cfg, int n) {
   if (n < 2 || nodes[0].type != AD_FXN_INPUT) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: node 0 must be the input");
   // consumers of each (node, port)
@@ -262,8 +302,9 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
   int out_node = -1;
   for (int i = 0; i < n; ++i) {
     const ad_fx_node& d = nodes[i];
-    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_PITCHSPEC || (d.type > AD_FXN_RINGMOD && d.type < AD_FXN_DISTORTION) ||
-        (d.type > AD_FXN_BITCRUSHER && d.type < AD_FXN_DEESSER))
+    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_VOCODER || (d.type > AD_FXN_RINGMOD && d.type < AD_FXN_DISTORTION) ||
+        (d.type > AD_FXN_BITCRUSHER && d.type < AD_FXN_DEESSER) ||
+        (d.type > AD_FXN_PITCHSPEC && d.type < AD_FXN_LOOKAHEAD))
       AD_FAIL(AD_ERR_UNKNOWN_EFFECT, "fx graph: node type not supported by the GPU runtime");
     if (d.type == AD_FXN_INPUT && i != 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: more than one input node");
     if (d.type == AD_FXN_OUTPUT) {
@@ -325,6 +366,26 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
       const ad_pitchspec_config* c = node_cfg<ad_pitchspec_config>(cfg, i);
       if (!c || ad_pitchspec_validate(c) != AD_OK)
         AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: spectral pitch shifter node without a valid config of its size");
+    }
+    if (d.type == AD_FXN_LOOKAHEAD) {
+      const ad_fx_lookahead_node* c = node_cfg<ad_fx_lookahead_node>(cfg, i);
+      if (!c || ad_lookahead_validate(&c->config) != AD_OK)
+        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: lookahead limiter node without a valid config of its size");
+    }
+    if (d.type == AD_FXN_VOCODER) {
+      const ad_fx_vocoder_node* c = node_cfg<ad_fx_vocoder_node>(cfg, i);
+      if (!c || ad_vocoder_validate(&c->config) != AD_OK)
+        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: vocoder node without a valid config of its size");
+    }
+    // a side consumer counts: a parent it reads is not rewritten in place by that parent's main consumer
+    const Side side = side_of(nodes, cfg, i);
+    if (side.n < 0 || side.n > AD_FX_MAX_PARENTS) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: bad side parent list");
+    for (int k = 0; k < side.n; ++k) {
+      const int p = side.parents[k], port = side.ports[k];
+      if (p < 0 || p >= i) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: side parents must precede their node");
+      if (port != 0 && !(port == 1 && nodes[p].type == AD_FXN_SPLIT_FREQ))
+        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: port 1 exists only on split-freq nodes");
+      uses[(size_t)p * 2 + port]++;
     }
     if (d.type == AD_FXN_COMPRESSOR && (d.dyn_mode < 0 || d.dyn_mode > 2))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: bad dynamics mode");
@@ -520,6 +581,40 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
       g->ops.push_back(op);
       continue;
     }
+    if (d.type == AD_FXN_LOOKAHEAD || d.type == AD_FXN_VOCODER) {
+      flush(g, gr);
+      // the side input (processSidechainNode chain_process.go:249-256): one side parent is read where it
+      // lies, several mix into a buffer of their own; none means the node's own input, which the limiter
+      // takes as "no sidechain" and the vocoder as one pointer for both inputs (a workgroup reads its samples
+      // before it stores them)
+      const Side side = side_of(nodes, cfg, i);
+      int sb = -1;
+      if (side.n == 1) {
+        sb = buf_of[(size_t)side.parents[0] * 2 + side.ports[0]];
+      } else if (side.n > 1) {
+        sb = g->nbuf++;
+        FxOp mix{FxOp::MIX};
+        mix.dst = sb;
+        for (int k = 0; k < side.n; ++k) mix.srcs.push_back(buf_of[(size_t)side.parents[k] * 2 + side.ports[k]]);
+        g->ops.push_back(mix);
+      }
+      FxOp op{d.type == AD_FXN_LOOKAHEAD ? FxOp::LOOKAHEAD : FxOp::VOCODER};
+      op.dst = b;
+      if (sb >= 0) op.srcs.push_back(sb);
+      if (d.type == AD_FXN_LOOKAHEAD) {
+        ad_lookahead* la = nullptr;
+        ck(ad_lookahead_create(&node_cfg<ad_fx_lookahead_node>(cfg, i)->config, g->channels, g->device, &la));
+        g->lookaheads.emplace_back(la);
+        op.lookahead = la;
+      } else {
+        ad_vocoder* vc = nullptr;
+        ck(ad_vocoder_create(&node_cfg<ad_fx_vocoder_node>(cfg, i)->config, g->channels, g->device, &vc));
+        g->vocoders.emplace_back(vc);
+        op.vocoder = vc;
+      }
+      g->ops.push_back(op);
+      continue;
+    }
     const int lvl = d.type == AD_FXN_BIQUAD ? 1 : (d.type == AD_FXN_COMPRESSOR ? 2 : 3);
     if (gr.open && (lvl < gr.level() || (lvl == gr.level() && lvl > 1))) flush(g, gr);
     gr.open = true;
@@ -689,6 +784,18 @@ void run(ad_fx_graph* g, double* d0, int64_t stride0, int64_t n, hipStream_t s) 
       case FxOp::PITCHSPEC:
         ck(ad_pitchspec_process_device(op.pitchspec, dst, st(op.dst), n, ls));
         break;
+      case FxOp::LOOKAHEAD: {
+        const bool has = !op.srcs.empty();
+        ck(ad_lookahead_process_device(op.lookahead, dst, st(op.dst), has ? buf_ptr(g, op.srcs[0], d0) : nullptr,
+                                       has ? st(op.srcs[0]) : 0, has ? n : 0, n, ls));
+        break;
+      }
+      case FxOp::VOCODER: {
+        const bool has = !op.srcs.empty();
+        ck(ad_vocoder_process_device(op.vocoder, dst, st(op.dst), has ? buf_ptr(g, op.srcs[0], d0) : dst,
+                                     has ? st(op.srcs[0]) : st(op.dst), dst, st(op.dst), n, ls));
+        break;
+      }
     }
     if (op.signal) AD_HIP(hipEventRecord(g->op_ev[i], ls));
   }
@@ -787,6 +894,8 @@ int ad_fx_graph_reset(ad_fx_graph* g) {
     for (auto& f : g->transients) ck(ad_transient_reset(f.get()));
     for (auto& f : g->specfreezes) ck(ad_specfreeze_reset(f.get()));
     for (auto& f : g->pitchspecs) ck(ad_pitchspec_reset(f.get()));
+    for (auto& f : g->lookaheads) ck(ad_lookahead_reset(f.get()));
+    for (auto& f : g->vocoders) ck(ad_vocoder_reset(f.get()));
   });
 }
 

@@ -24,6 +24,12 @@
 //                    de-esser's least gain of the call goes through a partial
 //                    per workgroup into metrics.GainReduction (k_deesser_gr).
 //
+// The lookahead limiter (lookahead_limiter.go:191-210) takes the same two
+// passes: k_dyn_walk<LimiterWalker> is the detector envelope of the sidechain
+// rows, k_lookahead_point the gain times the program D samples before, read
+// from a copy and a history so that in place no thread reads what another
+// writes (capi_lookahead.cpp).
+//
 // Every global index is guarded by the row's length and the channel count; a
 // scratch row has pitch >= n + 1 entries and is written at columns 0..n only.
 #include "dynfx_kernels.hpp"
@@ -57,6 +63,28 @@ struct TransientWalker {
     const double d = x - env;
     const double ea = env + attack * d, er = env + release * d;
     env = x > env ? ea : er;
+    o[0] = env;
+  }
+  __device__ void save(const DynWalkArgs& a, int64_t ch) { a.env[ch] = env; }
+  static __device__ double* out_base(const DynWalkArgs& a, int) { return a.env_s + 1; }
+  static __device__ int64_t out_pitch(const DynWalkArgs& a, int) { return a.pitch; }
+};
+
+// The limiter's detector (dynamics core.go:331-359, feed-forward, peak, no prefilter): the envelope of |sidechain|.
+struct LimiterWalker {
+  static constexpr int kTile = kDynWalkTile, kOut = 1;
+  double env, attack, release;
+  __device__ void load(const DynWalkArgs& a, int64_t ch, bool active) {
+    env = a.env[ch];
+    attack = a.attack;
+    release = a.release;
+    if (active) a.env_s[ch * a.pitch] = env;
+  }
+  __device__ __forceinline__ void step(double in, double (&o)[kOut]) {  // :352-356
+#pragma clang fp contract(off)
+    const double level = fabs(in);
+    const double ea = env + (level - env) * attack, er = level + (env - level) * release;
+    env = level > env ? ea : er;
     o[0] = env;
   }
   __device__ void save(const DynWalkArgs& a, int64_t ch) { a.env[ch] = env; }
@@ -318,6 +346,29 @@ __global__ __launch_bounds__(kDynPointThreads) void k_deesser_point(DeessPointAr
   }
 }
 
+// lookahead_limiter.go:197-209 from env_s: the gain of sample t times the program sample D before it.  The
+// program comes from a copy (prog_s) and, for its first D samples, from the history of the calls before, so
+// no thread reads a sample of buf that another one writes.
+__global__ __launch_bounds__(kDynPointThreads) void k_lookahead_point(LookaheadPointArgs a, int tiles) {
+#pragma clang fp contract(off)
+  const int64_t ch = blockIdx.x / tiles;
+  const int tile = (int)(blockIdx.x % tiles);
+  if (ch >= a.channels) return;
+  double* row = a.buf + ch * a.stride;
+  const double* env = a.env_s + ch * a.pitch + 1;
+  const double* prog = a.prog_s + ch * a.prog_pitch;
+  const double* hist = a.hist + ch * a.delay;  // the D samples before the call, oldest first
+  const int64_t p0 = (int64_t)tile * kDynPointSpan + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kDynPointSteps; ++k) {
+    const int64_t t = p0 + (int64_t)k * kDynPointThreads;
+    if (t >= a.n) break;
+    const double gain = deess_gain(a.g, env[t]);  // GainForLevel core.go:288-309 with knee 0
+    const double delayed = t >= a.delay ? prog[t - a.delay] : hist[t];
+    row[t] = delayed * gain;
+  }
+}
+
 // metrics.GainReduction over the call's gains (:442-444).  A gain is at most 1
 // and, within a call, a NaN gain is followed by NaN gains only (a NaN envelope
 // stays one), so the sequential rule is: the least of the finite gains and the
@@ -371,6 +422,17 @@ void launch_deesser_walk(const DynWalkArgs& a, hipStream_t s) {
     case 3: return launch_deesser_walk_o<3>(a, s);
     case 4: return launch_deesser_walk_o<4>(a, s);
   }
+}
+
+void launch_limiter_walk(const DynWalkArgs& a, hipStream_t s) {
+  if (a.n <= 0 || a.channels <= 0) return;
+  k_dyn_walk<LimiterWalker><<<dim3((unsigned)((a.channels + 63) / 64)), dim3(64), 0, s>>>(a);
+}
+
+void launch_lookahead_point(const LookaheadPointArgs& a, hipStream_t s) {
+  if (a.n <= 0 || a.channels <= 0) return;
+  const int tiles = deess_point_tiles(a.n);
+  k_lookahead_point<<<dim3((unsigned)((int64_t)a.channels * tiles)), dim3(kDynPointThreads), 0, s>>>(a, tiles);
 }
 
 int deess_point_tiles(int64_t n) { return (int)std::max<int64_t>(1, (n + kDynPointSpan - 1) / kDynPointSpan); }

@@ -78,6 +78,23 @@ struct DeessPointArgs {
 int deess_point_tiles(int64_t n);
 void launch_deesser_point(const DeessPointArgs& a, hipStream_t s);
 
+// The lookahead limiter (lookahead_limiter.go:191-210): the detector's envelope of n samples of buf (the
+// sidechain rows, read only) into env_s as the other walks leave it, then the gain times the delayed program.
+void launch_limiter_walk(const DynWalkArgs& a, hipStream_t s);
+struct LookaheadPointArgs {
+  double* buf;  // [channels][stride]: the program, rewritten
+  int64_t stride, n;
+  const double* prog_s;  // [channels][prog_pitch]: the call's program samples, copied before
+  int64_t prog_pitch;
+  const double* hist;  // [channels][delay]: the program's last `delay` samples of the calls before
+  int64_t delay;       // D = round(lookaheadMs * fs / 1000)
+  const double* env_s;
+  int64_t pitch;
+  DeessGainParams g;  // knee off, range_lin 0: GainForLevel core.go:288-309
+  int channels;
+};
+void launch_lookahead_point(const LookaheadPointArgs& a, hipStream_t s);
+
 // gains[i] = calculateGain(levels[i]) over device arrays [n].
 void launch_deesser_gain(const DeessGainParams& g, const double* levels, double* gains, int64_t n, hipStream_t s);
 

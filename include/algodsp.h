@@ -599,6 +599,11 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
                                 at create), an op of its own */
 #define AD_FXN_PITCHSPEC 21  /* pitch-spectral: an ad_pitchspec created from cfg[i] (its window and resampling
                                 prototype are read at create), an op of its own */
+/* 22 is not assigned: it stays AD_ERR_UNKNOWN_EFFECT */
+#define AD_FXN_LOOKAHEAD 23  /* dyn-lookahead: an ad_lookahead created from cfg[i] (an ad_fx_lookahead_node), an op
+                                of its own that reads its side parents */
+#define AD_FXN_VOCODER 24    /* vocoder: an ad_vocoder created from cfg[i] (an ad_fx_vocoder_node); the node's
+                                buffer is the modulator, the side parents mix into the carrier */
 #define AD_FX_MAX_PARENTS 8
 struct ad_fdn_config;
 struct ad_delay_config;
@@ -1214,6 +1219,152 @@ int ad_deesser_process(ad_deesser* d, double* buf, int64_t n);
 int ad_deesser_process_device(ad_deesser* d, double* d_buf, int64_t stride, int64_t n, void* stream);
 int ad_deesser_reset(ad_deesser* d);
 void ad_deesser_destroy(ad_deesser* d);
+
+/* ---- effects.Vocoder (dsp/effects/vocoder.go) --------------------------------
+ * For `channels` instances sharing one configuration; each channel has its
+ * own modulator row, carrier row and state.  One channel is up to 32 band
+ * recurrences whose products are summed per sample, so a channel is walked by
+ * one wave with a band per lane: lanes 0..31 carry the modulator side of band
+ * b (analysis section and envelope; with downsampling the group's anti-alias
+ * section, then the decimated analysis section and envelope on the group's
+ * ticks), lanes 32..63 the carrier side (synthesis section).  A second phase
+ * forms the band-order sum and the mix, one sample per lane.  Every product
+ * and sum is rounded on its own (no FMA): a call is bit for bit ProcessBlock
+ * :634-645 given the tables of ad_vocoder_derived, which come from the C
+ * library's cos, sin and exp in the reference's operation order.
+ * config: layout 0 ThirdOctave / 1 Bark (:15-25); synth_q is used by
+ *   ThirdOctave always and by Bark only when synth_q_set (:381-384);
+ *   downsample 0 / 1 (WithDownsampling :90).
+ * validate: the options' own ranges (:49-56, :98-193), the sample rate
+ *   positive and finite, and at least one usable band (:320, :361); host only.
+ * set_param: the named setter with its own check.  SAMPLE_RATE (:673-683)
+ *   clears the envelopes and every section's state (and the counter when
+ *   downsampling is on); a rate that leaves no usable band is refused and
+ *   changes nothing (the reference leaves a broken instance behind).
+ *   DOWNSAMPLING (:737-769) takes 0 or 1: on, it rebuilds the decimated
+ *   analysis sections, the anti-alias sections and the counter, also when it
+ *   was on already, and keeps the envelopes and the full-rate sections; off,
+ *   it zeroes the counter.  The layout and the synthesis Q have no setter in
+ *   the reference and none here.
+ * process: host rows [channels][n] each; out may be modulator or carrier.
+ * process_device: device rows [channels][stride]; out may be exactly the
+ *   modulator's or the carrier's rows (same pointer and stride) or rows that
+ *   overlap neither; asynchronous on `stream`.
+ * reset: Reset :648-670. */
+#define AD_VOCODER_MAX_BANDS 32
+typedef struct ad_vocoder ad_vocoder;
+typedef struct ad_vocoder_config {
+  double sample_rate, synth_q, attack_ms, release_ms, input_level, synth_level, vocoder_level;
+  int downsample, layout, synth_q_set;
+} ad_vocoder_config;
+#define AD_VOCODER_SAMPLE_RATE 0   /* SetSampleRate vocoder.go:673 */
+#define AD_VOCODER_ATTACK 2        /* SetAttack vocoder.go:772 */
+#define AD_VOCODER_RELEASE 3       /* SetRelease vocoder.go:786 */
+#define AD_VOCODER_INPUT_LEVEL 4   /* SetInputLevel vocoder.go:800 */
+#define AD_VOCODER_SYNTH_LEVEL 5   /* SetSynthLevel vocoder.go:812 */
+#define AD_VOCODER_VOCODER_LEVEL 6 /* SetVocoderLevel vocoder.go:824 */
+#define AD_VOCODER_DOWNSAMPLING 7  /* SetDownsampling vocoder.go:737 */
+/* What the reference caches for a config: sections are {b0, b1, b2, a1, a2}.  With downsampling off num_groups
+ * and downsample_max are 0 and the decimation entries are zero. */
+typedef struct ad_vocoder_tables {
+  int num_bands, num_groups, downsample_max;
+  int factors[AD_VOCODER_MAX_BANDS];       /* downsampleFactors, by band */
+  int group_of_band[AD_VOCODER_MAX_BANDS]; /* index into group_factors */
+  int group_factors[AD_VOCODER_MAX_BANDS]; /* downsampleGroupFactors, ascending */
+  double analysis[AD_VOCODER_MAX_BANDS][5], synthesis[AD_VOCODER_MAX_BANDS][5];
+  double decimated[AD_VOCODER_MAX_BANDS][5]; /* downsampleAnalysisFilters, by band */
+  double antialias[AD_VOCODER_MAX_BANDS][5]; /* downsampleGroupAAFilters, by group */
+  double attack_coeff, release_coeff;
+  double ds_attack[AD_VOCODER_MAX_BANDS], ds_release[AD_VOCODER_MAX_BANDS];
+} ad_vocoder_tables;
+void ad_vocoder_default_config(ad_vocoder_config* cfg, double sample_rate);
+int ad_vocoder_validate(const ad_vocoder_config* cfg);
+int ad_vocoder_derived(const ad_vocoder_config* cfg, ad_vocoder_tables* out);
+int ad_vocoder_create(const ad_vocoder_config* cfg, int channels, int device, ad_vocoder** out);
+int ad_vocoder_set_param(ad_vocoder* v, int which, double value);
+int ad_vocoder_get_config(const ad_vocoder* v, ad_vocoder_config* cfg);
+int ad_vocoder_num_bands(const ad_vocoder* v, int* num_bands);
+/* DownsampleFactors :722-731: *count = 0 with downsampling off, else NumBands factors into factors[cap]. */
+int ad_vocoder_downsample_factors(const ad_vocoder* v, int* factors, int cap, int* count);
+int ad_vocoder_kernel_info(const ad_vocoder* v, int* lanes_per_channel, int* tile, int* lds_bytes);
+/* One channel's state: {analysis s0, s1, synthesis s0, s1, decimated s0, s1, envelope} by band, then the
+ * anti-alias {s0, s1} by group: state[9][AD_VOCODER_MAX_BANDS]; *counter: downsampleCount. */
+int ad_vocoder_get_state(ad_vocoder* v, int channel, double* state, int* counter);
+int ad_vocoder_process(ad_vocoder* v, const double* modulator, const double* carrier, double* out, int64_t n);
+int ad_vocoder_process_device(ad_vocoder* v, const double* d_modulator, int64_t modulator_stride,
+                              const double* d_carrier, int64_t carrier_stride, double* d_out, int64_t out_stride,
+                              int64_t n, void* stream);
+int ad_vocoder_reset(ad_vocoder* v);
+void ad_vocoder_destroy(ad_vocoder* v);
+
+/* ---- dynamics.LookaheadLimiter (dsp/effects/dynamics/lookahead_limiter.go) ----
+ * For `channels` instances sharing one configuration.  The limiter is a
+ * Compressor core fixed at ratio 100, attack 0.1 ms, knee 0 and no makeup
+ * (:42-70), feed-forward with the peak detector.  Its gain comes from the
+ * sidechain sample (core.ProcessSample(0, sidechain) :197) and multiplies the
+ * program delayed by D = round(lookahead_ms * sample_rate / 1000) samples,
+ * halves away from zero as math.Round.  A call is three passes: the envelope
+ * of |sidechain| (serial in time, one channel per lane, the de-esser's walk),
+ * a copy of the call's program samples, and a pointwise pass that writes
+ * gain(env[t]) * program[t - D] in place, the first D samples from a
+ * per-channel history of the calls before.  The copy is what makes in place
+ * safe: no thread reads a program sample another one writes.
+ * The envelope, the delayed samples and the product are bit for bit the
+ * reference's; the gain (GainForLevel core.go:288-309) differs from it by the
+ * device math library's log and exp2 only, as the de-esser's.
+ * set_param: the named setter with its own range (:8-19, :98-161).  LOOKAHEAD
+ *   and SAMPLE_RATE rebuild the delay line zeroed, also when the value is
+ *   unchanged (rebuildDelayBuffer :232-239); the envelope stays.
+ * process / process_device: the program rows in place; sidechain NULL: the
+ *   program is its own detector (ProcessInPlace :213); else rows of
+ *   sidechain_n samples, read as 0 from there on (ProcessInPlaceSidechain
+ *   :221-230), which must not overlap the program rows.
+ * ad_lookahead_gain: gains[i] = GainForLevel(levels[i]) for host arrays, by
+ *   the device code a call runs.  Nothing advances.
+ * ad_lookahead_last_envelope: the detector envelope of every sample of the
+ *   last call, [channels][n] with n that call's length (a call short enough
+ *   for one pass; else AD_ERR_INVALID_ARGUMENT).
+ * reset: Reset :176-183: the envelope and the delay line. */
+typedef struct ad_lookahead ad_lookahead;
+typedef struct ad_lookahead_config {
+  double sample_rate, threshold_db, release_ms, lookahead_ms;
+} ad_lookahead_config;
+#define AD_LOOKAHEAD_SAMPLE_RATE 0 /* SetSampleRate lookahead_limiter.go:146 */
+#define AD_LOOKAHEAD_THRESHOLD 1   /* SetThreshold :99 */
+#define AD_LOOKAHEAD_RELEASE 2     /* SetRelease :116 */
+#define AD_LOOKAHEAD_LOOKAHEAD 3   /* SetLookahead :133 */
+void ad_lookahead_default_config(ad_lookahead_config* cfg, double sample_rate);
+int ad_lookahead_validate(const ad_lookahead_config* cfg);
+int ad_lookahead_derived(const ad_lookahead_config* cfg, double* attack_coeff, double* release_coeff,
+                         double* threshold_log2, int64_t* delay_samples);
+int ad_lookahead_create(const ad_lookahead_config* cfg, int channels, int device, ad_lookahead** out);
+int ad_lookahead_set_param(ad_lookahead* l, int which, double value);
+int ad_lookahead_get_config(const ad_lookahead* l, ad_lookahead_config* cfg);
+int ad_lookahead_get_state(ad_lookahead* l, int channel, double* envelope);
+int ad_lookahead_gain(ad_lookahead* l, const double* levels, double* gains, int64_t n);
+int ad_lookahead_last_envelope(ad_lookahead* l, double* envelope, int64_t n);
+int ad_lookahead_process(ad_lookahead* l, double* program, const double* sidechain, int64_t sidechain_n, int64_t n);
+int ad_lookahead_process_device(ad_lookahead* l, double* d_program, int64_t stride, const double* d_sidechain,
+                                int64_t sidechain_stride, int64_t sidechain_n, int64_t n, void* stream);
+int ad_lookahead_reset(ad_lookahead* l);
+void ad_lookahead_destroy(ad_lookahead* l);
+
+/* The graph nodes with a second input (chain_process.go:124-175, 226-259): cfg[i] of an AD_FXN_LOOKAHEAD or
+ * AD_FXN_VOCODER node.  The node's `parents` are its main parents (the edges whose toPortIndex is not 1) and mix
+ * into its buffer as every node's do; side_parents are the edges with toPortIndex 1, in edge order, and mix the
+ * same way (a copy for one, the edge-order sum times 1/k for more) into the side input: the limiter's detector,
+ * the vocoder's carrier (runtime_misc.go:122-124).  side_ports[k] 1: the high band of a split-freq parent.
+ * n_side 0: the side input is the node's own mixed input.  A bypassed node mixes its main parents only.  Unlike
+ * the reference, whose splitMainAndSideParents filters the node's incoming list in place and so loses a side
+ * edge listed before a main edge from the second block on, the rule holds for every block. */
+typedef struct ad_fx_lookahead_node {
+  ad_lookahead_config config;
+  int n_side, side_parents[AD_FX_MAX_PARENTS], side_ports[AD_FX_MAX_PARENTS];
+} ad_fx_lookahead_node;
+typedef struct ad_fx_vocoder_node {
+  ad_vocoder_config config;
+  int n_side, side_parents[AD_FX_MAX_PARENTS], side_ports[AD_FX_MAX_PARENTS];
+} ad_fx_vocoder_node;
 
 /* ---- crossover.MultiBand, dynamics.MultibandCompressor (dsp/filter/crossover/
  * crossover.go:113-222, dsp/effects/dynamics/multiband.go) ----------------------
