@@ -13,9 +13,8 @@
 #include <utility>
 #include <vector>
 
-#include "ad_common.hpp"
-#include "stream_order.hpp"
 #include "delayfx_kernels.hpp"
+#include "fx_handle.hpp"
 
 using namespace adsp;
 
@@ -38,15 +37,13 @@ constexpr int kDelayCrossover = 256;
 
 const double kTwoPi = 2.0 * M_PI;
 
-bool finite(double v) { return std::isfinite(v); }
-
 double smooth_coeff(double fs) { return 1 - std::exp(-1 / (fs * kSmoothSeconds)); }  // computeSmoothCoeff :255-257
 
 void validate_time(double v) {  // validateTime :191-199
   if (!(v >= kMinTime && v <= kMaxTime)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "delay time must be in [0.001, 2]");
 }
 void validate_delay_rate(double v) {
-  if (!(v > 0) || !finite(v)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "delay sample rate must be > 0");
+  if (!(v > 0) || !is_finite(v)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "delay sample rate must be > 0");
   if (!(std::ceil(kMaxTime * v) + 1 <= kMaxRing)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "delay: a ring longer than 2^27 samples");
 }
 void validate_feedback(double v) {  // SetFeedback :109-117
@@ -76,10 +73,10 @@ int flanger_needed(const ad_flanger_config& c) {  // reconfigureDelayLine :358
 }
 
 void validate(const ad_flanger_config& c) {  // validateParams :317-350
-  if (!(c.sample_rate > 0) || !finite(c.sample_rate))
+  if (!(c.sample_rate > 0) || !is_finite(c.sample_rate))
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "flanger sample rate must be > 0 and finite");
-  if (!(c.rate_hz > 0) || !finite(c.rate_hz)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "flanger rate must be > 0 and finite");
-  if (!(c.depth_seconds >= 0) || !finite(c.depth_seconds))
+  if (!(c.rate_hz > 0) || !is_finite(c.rate_hz)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "flanger rate must be > 0 and finite");
+  if (!(c.depth_seconds >= 0) || !is_finite(c.depth_seconds))
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "flanger depth must be >= 0 and finite");
   if (!(c.base_delay_seconds >= kMinFlangerDelay && c.base_delay_seconds <= kMaxFlangerDelay))
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "flanger base delay must be in [0.0001, 0.01]");
@@ -110,52 +107,21 @@ void resize_ring(DevBuf<double>& ring, int channels, int old_len, int old_wp, in
 
 }  // namespace
 
-struct ad_delay {
-  int device = 0, channels = 0;
+struct ad_delay : HandleCore {
   ad_delay_config cfg{};             // time_seconds: delaySeconds; smooth_coeff: the coefficient in use
   double target = 0, current = 0;    // targetSamples, currentSamples
   int len = 0, wp = 0;               // ring length (mode 1: D slots), write position of every channel
   DevBuf<double> ring;               // [channels][len]
-  DevBuf<double> traj;               // the call's ramp
-  double* traj_host = nullptr;       // pinned; reused once traj_ev has passed
-  size_t traj_cap = 0;
-  hipEvent_t traj_ev = nullptr;
-  bool traj_pending = false;
+  PinnedUpload traj;                 // the call's ramp
   int force_regime = 0, last_regime = 0, last_launches = 0;
-  hipStream_t stream = nullptr;  // host-buffer calls, resets, resizes
-  StreamOrder order;             // calls may come on any stream
-  DevBuf<double> io;             // host-buffer calls
-  ~ad_delay() {
-    order.release();
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      (void)lib_stream_destroy(stream);
-    }
-    if (traj_ev) {
-      (void)hipEventSynchronize(traj_ev);
-      (void)hipEventDestroy(traj_ev);
-    }
-    if (traj_host) (void)hipHostFree(traj_host);
-  }
 };
 
-struct ad_flanger {
-  int device = 0, channels = 0;
+struct ad_flanger : HandleCore {
   ad_flanger_config cfg{};
   int len = 0, wp = 0;
   DevBuf<double> ring;   // [channels][len]
   DevBuf<double> phase;  // [2]: lfoPhase, ping-pong (cur = phase[ph_cur])
   int ph_cur = 0;
-  hipStream_t stream = nullptr;
-  StreamOrder order;
-  DevBuf<double> io;
-  ~ad_flanger() {
-    order.release();
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      (void)lib_stream_destroy(stream);
-    }
-  }
 };
 
 namespace {
@@ -194,7 +160,7 @@ Blocks blocks_of(const ad_delay* f) {
 void delay_run(ad_delay* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
 #pragma clang fp contract(off)
   if (f->cfg.mode == 1 && f->cfg.delay_samples == 0) return;  // Process returns at once (:347-349)
-  f->order.enter(s);
+  CallScope call(f->order, s);
   const Blocks b = blocks_of(f);  // before the ramp moves `current`
   // the ramp (:142), one rounded subtraction, product and sum per sample, up to its fixed point
   std::vector<double> ramp;
@@ -209,22 +175,8 @@ void delay_run(ad_delay* f, double* d_buf, int64_t stride, int64_t n, hipStream_
     }
   }
   if (!ramp.empty()) {
-    if (f->traj_pending) AD_HIP(hipEventSynchronize(f->traj_ev));
-    f->traj_pending = false;
-    if (ramp.size() > f->traj_cap) {
-      if (f->traj_host) AD_HIP(hipHostFree(f->traj_host));
-      f->traj_host = nullptr;
-      f->traj_cap = 0;
-      const size_t cap = std::max<size_t>(ramp.size(), 4096);
-      AD_HIP(hipHostMalloc(reinterpret_cast<void**>(&f->traj_host), cap * sizeof(double), hipHostMallocDefault));
-      f->traj_cap = cap;
-      f->traj.reserve(cap);  // hipFree waits for the device, so no earlier call still reads the old one
-    }
-    std::memcpy(f->traj_host, ramp.data(), ramp.size() * sizeof(double));
-    AD_HIP(hipMemcpyAsync(f->traj.p, f->traj_host, ramp.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    if (!f->traj_ev) AD_HIP(hipEventCreateWithFlags(&f->traj_ev, hipEventDisableTiming));
-    AD_HIP(hipEventRecord(f->traj_ev, s));
-    f->traj_pending = true;
+    std::memcpy(f->traj.stage(ramp.size()), ramp.data(), ramp.size() * sizeof(double));
+    f->traj.send(ramp.size(), s);
   }
   DelayArgs a{};
   a.buf = d_buf;
@@ -233,7 +185,7 @@ void delay_run(ad_delay* f, double* d_buf, int64_t stride, int64_t n, hipStream_
   a.ring = f->ring.p;
   a.len = f->len;
   a.wp = f->wp;
-  a.traj = f->traj.p;
+  a.traj = f->traj.dev.p;
   a.ntraj = (int64_t)ramp.size();
   a.c_rest = c;
   a.feedback = f->cfg.feedback;
@@ -255,7 +207,6 @@ void delay_run(ad_delay* f, double* d_buf, int64_t stride, int64_t n, hipStream_
   f->current = c;
   f->last_regime = regime;
   f->last_launches = launches;
-  f->order.leave(s);
 }
 
 // ---- flanger ----------------------------------------------------------------
@@ -275,7 +226,7 @@ void reconfigure_line(ad_flanger* f) {
 }
 
 void flanger_run(ad_flanger* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
-  f->order.enter(s);
+  CallScope call(f->order, s);
   FlangerArgs a{};
   a.buf = d_buf;
   a.stride = stride;
@@ -299,7 +250,6 @@ void flanger_run(ad_flanger* f, double* d_buf, int64_t stride, int64_t n, hipStr
   AD_HIP(hipGetLastError());
   f->wp = (int)((f->wp + n) % f->len);
   f->ph_cur ^= 1;
-  f->order.leave(s);
 }
 
 double* field(ad_flanger_config& c, int which) {
@@ -312,17 +262,6 @@ double* field(ad_flanger_config& c, int which) {
     case AD_FLANGER_MIX: return &c.mix;
   }
   return nullptr;
-}
-
-// host-buffer call through the handle's staging buffer and stream
-template <class H, class Run>
-void host_call(H* f, double* buf, int64_t n, Run run) {
-  const size_t count = (size_t)f->channels * n;
-  f->io.reserve(count);
-  AD_HIP(hipMemcpyAsync(f->io.p, buf, count * sizeof(double), hipMemcpyHostToDevice, f->stream));
-  run(f, f->io.p, n, n, f->stream);
-  AD_HIP(hipMemcpyAsync(buf, f->io.p, count * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-  AD_HIP(hipStreamSynchronize(f->stream));
 }
 
 }  // namespace
@@ -339,54 +278,30 @@ void ad_delay_default_config(ad_delay_config* cfg, double sample_rate) {
   cfg->mix = kDefaultMix;
 }
 
-int ad_delay_validate(const ad_delay_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null delay config");
-    validate(*cfg);
-  });
-}
+int ad_delay_validate(const ad_delay_config* cfg) { return validate_config(cfg, validate); }
 
 int ad_delay_create(const ad_delay_config* cfg, int channels, int device, ad_delay** out) {
-  if (out) *out = nullptr;
-  ad_delay* raw = nullptr;
-  const int rc = guard([&] {
-    if (!out) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null output handle");
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null delay config");
-    if (channels <= 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channels must be positive");
-    validate(*cfg);
-    const int dev = pick_device(device);
-    DeviceScope ds(dev);
-    std::unique_ptr<ad_delay> f(new ad_delay());
-    f->device = dev;
-    f->channels = channels;
-    f->cfg = *cfg;
-    AD_HIP(lib_stream_create(&f->stream));
-    if (cfg->mode == 1) {
-      if (cfg->delay_samples > 0) {
-        f->len = (int)cfg->delay_samples;
-        f->ring.alloc((size_t)channels * f->len);
-        AD_HIP(hipMemsetAsync(f->ring.p, 0, f->ring.n * sizeof(double), f->stream));
-        AD_HIP(hipStreamSynchronize(f->stream));
+  return create_handle(cfg, channels, device, out, validate, [](ad_delay* f, const ad_delay_config& c) {
+    if (c.mode == 1) {
+      if (c.delay_samples > 0) {
+        f->len = (int)c.delay_samples;
+        f->ring.alloc((size_t)f->channels * f->len);
+        zero(f->ring, f->stream);
       }
-      f->target = f->current = (double)cfg->delay_samples;
+      f->target = f->current = (double)c.delay_samples;
     } else {
       // NewDelay(sample_rate), then SetTargetTime(time_seconds) as configureDelay does
       if (f->cfg.smooth_coeff == 0) f->cfg.smooth_coeff = smooth_coeff(f->cfg.sample_rate);
       f->cfg.time_seconds = kDefaultTime;
-      reconfigure_buffer(f.get());
-      f->cfg.time_seconds = cfg->time_seconds;
-      f->target = std::round(cfg->time_seconds * cfg->sample_rate);
+      reconfigure_buffer(f);
+      f->cfg.time_seconds = c.time_seconds;
+      f->target = std::round(c.time_seconds * c.sample_rate);
     }
-    raw = f.release();
   });
-  if (rc == AD_OK && out) *out = raw;
-  return rc;
 }
 
 int ad_delay_set_param(ad_delay* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null delay handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     if (f->cfg.mode == 1) {
       // simpleDelayRuntime.Configure (:330-344): another length is a zeroed ring
       if (which != AD_DELAY_SAMPLES) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "delay-simple has one parameter, its delay in samples");
@@ -461,8 +376,7 @@ int ad_delay_get_config(const ad_delay* f, ad_delay_config* cfg) {
 
 int ad_delay_derived(const ad_delay* f, double* current_samples, double* target_samples, int64_t* ring_len,
                      int64_t* write_pos) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null delay handle");
+  return with_handle(f, [&] {
     if (current_samples) *current_samples = f->current;
     if (target_samples) *target_samples = f->target;
     if (ring_len) *ring_len = f->len;
@@ -471,8 +385,7 @@ int ad_delay_derived(const ad_delay* f, double* current_samples, double* target_
 }
 
 int ad_delay_kernel_info(const ad_delay* f, int* block, int* sub_block, int* regime, int* launches) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null delay handle");
+  return with_handle(f, [&] {
     const Blocks b = f->len > 0 ? blocks_of(f) : Blocks{1, 1};
     if (block) *block = b.both;
     if (sub_block) *sub_block = pow2_sub(b.raw);
@@ -482,52 +395,29 @@ int ad_delay_kernel_info(const ad_delay* f, int* block, int* sub_block, int* reg
 }
 
 int ad_delay_set_regime(ad_delay* f, int regime) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null delay handle");
+  return with_handle(f, [&] {
     if (regime < 0 || regime > 2) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "delay regime must be 0 (choose), 1 or 2");
     f->force_regime = regime;
   });
 }
 
-int ad_delay_process(ad_delay* f, double* buf, int64_t n) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null delay handle");
-    if (n < 0 || (n > 0 && !buf)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    host_call(f, buf, n, delay_run);
-  });
-}
+int ad_delay_process(ad_delay* f, double* buf, int64_t n) { return process_host(f, buf, n, delay_run); }
 
 int ad_delay_process_device(ad_delay* f, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null delay handle");
-    if (n < 0 || (n > 0 && (!d_buf || stride < n))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer geometry");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    delay_run(f, d_buf, stride, n, reinterpret_cast<hipStream_t>(stream));
-  });
+  return process_device(f, d_buf, stride, n, stream, delay_run);
 }
 
 int ad_delay_reset(ad_delay* f) {
   // Reset :131-137 (currentSamples stays); ordered after the last call, whatever stream it used
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null delay handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
-    if (f->ring.p) AD_HIP(hipMemsetAsync(f->ring.p, 0, f->ring.n * sizeof(double), f->stream));
+    zero(f->ring, f->stream);
     AD_HIP(hipStreamSynchronize(f->stream));
     f->wp = 0;
   });
 }
 
-void ad_delay_destroy(ad_delay* f) {
-  if (!f) return;
-  (void)guard([&] {
-    DeviceScope ds(f->device);
-    delete f;
-  });
-}
+void ad_delay_destroy(ad_delay* f) { destroy_handle(f); }
 
 // ---- ad_flanger -------------------------------------------------------------
 void ad_flanger_default_config(ad_flanger_config* cfg, double sample_rate) {
@@ -540,40 +430,18 @@ void ad_flanger_default_config(ad_flanger_config* cfg, double sample_rate) {
   cfg->mix = 0.5;
 }
 
-int ad_flanger_validate(const ad_flanger_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null flanger config");
-    validate(*cfg);
-  });
-}
+int ad_flanger_validate(const ad_flanger_config* cfg) { return validate_config(cfg, validate); }
 
 int ad_flanger_create(const ad_flanger_config* cfg, int channels, int device, ad_flanger** out) {
-  if (out) *out = nullptr;
-  ad_flanger* raw = nullptr;
-  const int rc = guard([&] {
-    if (!out) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null output handle");
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null flanger config");
-    if (channels <= 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channels must be positive");
-    validate(*cfg);
-    const int dev = pick_device(device);
-    DeviceScope ds(dev);
-    std::unique_ptr<ad_flanger> f(new ad_flanger());
-    f->device = dev;
-    f->channels = channels;
-    f->cfg = *cfg;
-    AD_HIP(lib_stream_create(&f->stream));
+  return create_handle(cfg, channels, device, out, validate, [](ad_flanger* f, const ad_flanger_config&) {
     f->phase.alloc(2);
-    AD_HIP(hipMemsetAsync(f->phase.p, 0, 2 * sizeof(double), f->stream));
-    reconfigure_line(f.get());
-    raw = f.release();
+    zero(f->phase, f->stream);
+    reconfigure_line(f);
   });
-  if (rc == AD_OK && out) *out = raw;
-  return rc;
 }
 
 int ad_flanger_set_param(ad_flanger* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null flanger handle");
+  return with_handle(f, [&] {
     ad_flanger_config c = f->cfg;
     double* v = field(c, which);
     if (!v) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "unknown flanger parameter");
@@ -584,7 +452,6 @@ int ad_flanger_set_param(ad_flanger* f, int which, double value) {
     const ad_flanger_config old = f->cfg;
     f->cfg = c;
     if (which == AD_FLANGER_SAMPLE_RATE || which == AD_FLANGER_DEPTH || which == AD_FLANGER_BASE_DELAY) {
-      DeviceScope ds(f->device);
       try {
         reconfigure_line(f);
       } catch (...) {
@@ -604,13 +471,11 @@ int ad_flanger_get_config(const ad_flanger* f, ad_flanger_config* cfg) {
 
 int ad_flanger_derived(const ad_flanger* f, int64_t* ring_len, int64_t* max_delay, int64_t* write_pos,
                        double* lfo_phase) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null flanger handle");
+  return with_handle(f, [&] {
     if (ring_len) *ring_len = f->len;
     if (max_delay) *max_delay = f->len - 3;
     if (write_pos) *write_pos = f->wp;
     if (lfo_phase) {
-      DeviceScope ds(f->device);
       f->order.wait_host();
       AD_HIP(hipMemcpy(lfo_phase, f->phase.p + f->ph_cur, sizeof(double), hipMemcpyDeviceToHost));
     }
@@ -619,8 +484,7 @@ int ad_flanger_derived(const ad_flanger* f, int64_t* ring_len, int64_t* max_dela
 
 int ad_flanger_kernel_info(const ad_flanger* f, int* block, int* sub_block, int* channels_per_workgroup,
                            int* lds_bytes) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null flanger handle");
+  return with_handle(f, [&] {
     const FlangerShape sh = flanger_shape(flanger_block(f), f->len, f->channels);
     if (block) *block = flanger_block(f);
     if (sub_block) *sub_block = sh.sub;
@@ -629,45 +493,23 @@ int ad_flanger_kernel_info(const ad_flanger* f, int* block, int* sub_block, int*
   });
 }
 
-int ad_flanger_process(ad_flanger* f, double* buf, int64_t n) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null flanger handle");
-    if (n < 0 || (n > 0 && !buf)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    host_call(f, buf, n, flanger_run);
-  });
-}
+int ad_flanger_process(ad_flanger* f, double* buf, int64_t n) { return process_host(f, buf, n, flanger_run); }
 
 int ad_flanger_process_device(ad_flanger* f, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null flanger handle");
-    if (n < 0 || (n > 0 && (!d_buf || stride < n))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer geometry");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    flanger_run(f, d_buf, stride, n, reinterpret_cast<hipStream_t>(stream));
-  });
+  return process_device(f, d_buf, stride, n, stream, flanger_run);
 }
 
 int ad_flanger_reset(ad_flanger* f) {
   // Reset :249-256: the line, the write position and the LFO phase
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null flanger handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
-    AD_HIP(hipMemsetAsync(f->ring.p, 0, f->ring.n * sizeof(double), f->stream));
-    AD_HIP(hipMemsetAsync(f->phase.p, 0, 2 * sizeof(double), f->stream));
+    zero(f->ring, f->stream);
+    zero(f->phase, f->stream);
     AD_HIP(hipStreamSynchronize(f->stream));
     f->wp = 0;
   });
 }
 
-void ad_flanger_destroy(ad_flanger* f) {
-  if (!f) return;
-  (void)guard([&] {
-    DeviceScope ds(f->device);
-    delete f;
-  });
-}
+void ad_flanger_destroy(ad_flanger* f) { destroy_handle(f); }
 
 }  // extern "C"

@@ -19,22 +19,14 @@
 #include <memory>
 #include <vector>
 
-#include "ad_common.hpp"
 #include "dynfx_kernels.hpp"
-#include "stream_order.hpp"
+#include "fx_handle.hpp"
 
 using namespace adsp;
 
 namespace {
 
 constexpr double kLog2Of10Div20 = 0.166096404744;  // compressor.go:27 (truncated literal, kept)
-constexpr size_t kScratchBytes = (size_t)256 << 20;  // the scratch rows of one pass: a call longer than this is cut
-constexpr int64_t kMinSegment = 1024;
-
-bool finite(double v) { return std::isfinite(v); }
-bool positive(double v) { return v > 0 && finite(v); }
-bool in_range(double v, double lo, double hi) { return v >= lo && v <= hi; }  // false for NaN
-bool flag(int v) { return v == 0 || v == 1; }
 
 void validate(const ad_transient_config& c) {
   if (!positive(c.sample_rate)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "transient shaper sample rate must be positive and finite");
@@ -51,7 +43,7 @@ void validate(const ad_deesser_config& c) {
   if (!in_range(c.freq_hz, 1000, 20000)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "de-esser frequency must be in [1000, 20000]");
   if (c.freq_hz >= c.sample_rate / 2) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "de-esser frequency must be < Nyquist");
   if (!in_range(c.q, 0.1, 10)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "de-esser Q must be in [0.1, 10]");
-  if (!finite(c.threshold_db)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "de-esser threshold must be finite");
+  if (!is_finite(c.threshold_db)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "de-esser threshold must be finite");
   if (!in_range(c.ratio, 1, 100)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "de-esser ratio must be in [1, 100]");
   if (!in_range(c.knee_db, 0, 12)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "de-esser knee must be in [0, 12]");
   if (!in_range(c.attack_ms, 0.01, 50)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "de-esser attack must be in [0.01, 50]");
@@ -87,9 +79,9 @@ void deesser_coeffs(const ad_deesser_config& c, double* attack, double* release)
 void deesser_section(const ad_deesser_config& c, double* sec) {
   const double fs = c.sample_rate, freq = c.freq_hz;
   for (int i = 0; i < 5; ++i) sec[i] = 0;
-  if (!positive(fs) || !(freq > 0) || freq >= fs / 2 || !finite(freq)) return;
+  if (!positive(fs) || !(freq > 0) || freq >= fs / 2 || !is_finite(freq)) return;
   double q = c.q;
-  if (q <= 0 || !finite(q)) q = 1 / std::sqrt(2.0);
+  if (q <= 0 || !is_finite(q)) q = 1 / std::sqrt(2.0);
   const double w0 = 2 * M_PI * freq / fs;
   const double cw = std::cos(w0), sw = std::sin(w0);
   const double alpha = sw / (2 * q);
@@ -100,7 +92,7 @@ void deesser_section(const ad_deesser_config& c, double* sec) {
     b0 = sw / 2, b1 = 0.0, b2 = -sw / 2;
   }
   const double a0 = 1 + alpha, a1 = -2 * cw, a2 = 1 - alpha;
-  if (a0 == 0 || !finite(a0)) return;
+  if (a0 == 0 || !is_finite(a0)) return;
   sec[0] = b0 / a0, sec[1] = b1 / a0, sec[2] = b2 / a0, sec[3] = a1 / a0, sec[4] = a2 / a0;
 }
 
@@ -126,25 +118,13 @@ DeessDerived deesser_derive(const ad_deesser_config& c) {
   return d;
 }
 
-// What the two handles share: the envelope, the scratch rows and the streams.
-struct DynCore {
-  int device = 0, channels = 0;
+// What the two handles share: the envelope and the scratch rows.
+struct DynCore : HandleCore {
   DevBuf<double> env;            // [channels]
   DevBuf<double> env_s, band_s;  // [channels][pitch] of one pass
-  hipStream_t stream = nullptr;  // host-buffer calls, resets, state access
-  StreamOrder order;             // calls may come on any stream
-  DevBuf<double> io;             // host-buffer calls
-  ~DynCore() {
-    order.release();
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      (void)lib_stream_destroy(stream);
-    }
-  }
-  // samples of a call one pass takes, so that `rows` scratch rows per channel stay within kScratchBytes
-  int64_t segment(int64_t n, int rows) const {
-    const int64_t fit = (int64_t)(kScratchBytes / ((size_t)channels * rows * sizeof(double))) - 1;
-    return std::min(n, std::max(fit, kMinSegment));
+  void init_env() {
+    env.alloc((size_t)channels);
+    zero(env, stream);
   }
 };
 
@@ -166,19 +146,9 @@ struct ad_deesser : DynCore {
 
 namespace {
 
-void fill(DevBuf<double>& b, double v, hipStream_t s) {
-  if (v == 0.0) {
-    AD_HIP(hipMemsetAsync(b.p, 0, b.n * sizeof(double), s));
-    return;
-  }
-  const std::vector<double> h(b.n, v);
-  AD_HIP(hipMemcpyAsync(b.p, h.data(), b.n * sizeof(double), hipMemcpyHostToDevice, s));
-  AD_HIP(hipStreamSynchronize(s));  // h leaves scope
-}
-
 void transient_run(ad_transient* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
-  f->order.enter(s);
-  const int64_t seg = f->segment(n, 1);
+  CallScope call(f->order, s);
+  const int64_t seg = scratch_segment(n, f->channels, 1);
   f->env_s.reserve((size_t)f->channels * (seg + 1));  // hipFree waits for the device, so no earlier call still reads the old one
   for (int64_t off = 0; off < n; off += seg) {
     const int64_t m = std::min(seg, n - off);
@@ -205,7 +175,6 @@ void transient_run(ad_transient* f, double* d_buf, int64_t stride, int64_t n, hi
     launch_transient_point(p, s);
   }
   AD_HIP(hipGetLastError());
-  f->order.leave(s);
 }
 
 int deesser_walk_mode(const ad_deesser* f) {
@@ -215,10 +184,10 @@ int deesser_walk_mode(const ad_deesser* f) {
 }
 
 void deesser_run(ad_deesser* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
-  f->order.enter(s);
+  CallScope call(f->order, s);
   const int mode = deesser_walk_mode(f);
   const bool split = mode == DEESS_SPLIT_ONE || mode == DEESS_SPLIT_TWO;
-  const int64_t seg = f->segment(n, 2);
+  const int64_t seg = scratch_segment(n, f->channels, 2);
   if (mode != DEESS_LISTEN) {
     f->env_s.reserve((size_t)f->channels * (seg + 1));
     if (split) f->band_s.reserve((size_t)f->channels * (seg + 1));
@@ -261,15 +230,13 @@ void deesser_run(ad_deesser* f, double* d_buf, int64_t stride, int64_t n, hipStr
   }
   AD_HIP(hipGetLastError());
   if (!split) f->diverged = true;  // detectFilters moved, bandFilters did not
-  f->order.leave(s);
 }
 
 // rebuildFilters :578-622: new sections, so both cascades start from zero; the envelope and the metrics stay
 void deesser_rebuild(ad_deesser* f) {
-  DeviceScope ds(f->device);
   f->order.wait_host();
-  AD_HIP(hipMemsetAsync(f->det.p, 0, f->det.n * sizeof(double), f->stream));
-  AD_HIP(hipMemsetAsync(f->band.p, 0, f->band.n * sizeof(double), f->stream));
+  zero(f->det, f->stream);
+  zero(f->band, f->stream);
   AD_HIP(hipStreamSynchronize(f->stream));
   f->diverged = false;
 }
@@ -279,79 +246,6 @@ void deesser_reset_metrics(ad_deesser* f) {
   fill(f->peak, 0.0, f->stream);
   fill(f->gr, 1.0, f->stream);
   AD_HIP(hipStreamSynchronize(f->stream));
-}
-
-template <class H, class Cfg>
-int create(const Cfg* cfg, int channels, int device, H** out, void (*init)(H*)) {
-  if (out) *out = nullptr;
-  H* raw = nullptr;
-  const int rc = guard([&] {
-    if (!out) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null output handle");
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null config");
-    if (channels <= 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channels must be positive");
-    validate(*cfg);
-    const int dev = pick_device(device);
-    DeviceScope ds(dev);
-    std::unique_ptr<H> f(new H());
-    f->device = dev;
-    f->channels = channels;
-    f->cfg = *cfg;
-    AD_HIP(lib_stream_create(&f->stream));
-    f->env.alloc((size_t)channels);
-    AD_HIP(hipMemsetAsync(f->env.p, 0, f->env.n * sizeof(double), f->stream));
-    init(f.get());
-    AD_HIP(hipStreamSynchronize(f->stream));
-    raw = f.release();
-  });
-  if (rc == AD_OK && out) *out = raw;
-  return rc;
-}
-
-template <class H, class Run>
-int process_host(H* f, double* buf, int64_t n, Run run) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || (n > 0 && !buf)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    const size_t count = (size_t)f->channels * n;
-    f->io.reserve(count);
-    AD_HIP(hipMemcpyAsync(f->io.p, buf, count * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    run(f, f->io.p, n, n, f->stream);
-    AD_HIP(hipMemcpyAsync(buf, f->io.p, count * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    AD_HIP(hipStreamSynchronize(f->stream));
-  });
-}
-
-template <class H, class Run>
-int process_dev(H* f, double* d_buf, int64_t stride, int64_t n, void* stream, Run run) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || (n > 0 && (!d_buf || stride < n))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer geometry");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    run(f, d_buf, stride, n, reinterpret_cast<hipStream_t>(stream));
-  });
-}
-
-template <class H>
-void destroy(H* f) {
-  if (!f) return;
-  (void)guard([&] {
-    DeviceScope ds(f->device);
-    delete f;
-  });
-}
-
-template <class H>
-void check_channel(const H* f, int channel) {
-  if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null handle");
-  if (channel < 0 || channel >= f->channels) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channel out of range");
-}
-
-int whole(double value, int lo, int hi, const char* msg) {
-  if (!in_range(value, lo, hi) || value != std::floor(value)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, msg);
-  return (int)value;
 }
 
 constexpr int walk_lds_bytes(int tile, int rows) { return 2 * rows * 64 * (tile + 1) * (int)sizeof(double); }
@@ -371,12 +265,7 @@ void ad_transient_default_config(ad_transient_config* cfg, double sample_rate) {
   cfg->release_ms = 120.0;
 }
 
-int ad_transient_validate(const ad_transient_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null transient shaper config");
-    validate(*cfg);
-  });
-}
+int ad_transient_validate(const ad_transient_config* cfg) { return validate_config(cfg, validate); }
 
 int ad_transient_derived(const ad_transient_config* cfg, double* attack_coeff, double* release_coeff) {
   return guard([&] {
@@ -390,14 +279,14 @@ int ad_transient_derived(const ad_transient_config* cfg, double* attack_coeff, d
 }
 
 int ad_transient_create(const ad_transient_config* cfg, int channels, int device, ad_transient** out) {
-  return create<ad_transient>(cfg, channels, device, out, +[](ad_transient* f) {
+  return create_handle(cfg, channels, device, out, validate, [](ad_transient* f, const ad_transient_config&) {
+    f->init_env();
     transient_coeffs(f->cfg, &f->cfg.attack_coeff, &f->cfg.release_coeff);
   });
 }
 
 int ad_transient_set_param(ad_transient* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null transient shaper handle");
+  return with_handle(f, [&] {
     ad_transient_config c = f->cfg;
     switch (which) {
       case AD_TRANSIENT_SAMPLE_RATE: c.sample_rate = value; break;        // SetSampleRate :107-117
@@ -429,8 +318,7 @@ int ad_transient_get_config(const ad_transient* f, ad_transient_config* cfg) {
 }
 
 int ad_transient_kernel_info(const ad_transient* f, int* channels_per_workgroup, int* tile, int* lds_bytes) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null transient shaper handle");
+  return with_handle(f, [&] {
     if (channels_per_workgroup) *channels_per_workgroup = 64;
     if (tile) *tile = kDynWalkTile;
     if (lds_bytes) *lds_bytes = walk_lds_bytes(kDynWalkTile, 1);
@@ -459,21 +347,19 @@ int ad_transient_set_state(ad_transient* f, int channel, double envelope) {
 int ad_transient_process(ad_transient* f, double* buf, int64_t n) { return process_host(f, buf, n, transient_run); }
 
 int ad_transient_process_device(ad_transient* f, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return process_dev(f, d_buf, stride, n, stream, transient_run);
+  return process_device(f, d_buf, stride, n, stream, transient_run);
 }
 
 int ad_transient_reset(ad_transient* f) {
   // Reset :135-137: the envelope; ordered after the last call
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null transient shaper handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
-    AD_HIP(hipMemsetAsync(f->env.p, 0, f->env.n * sizeof(double), f->stream));
+    zero(f->env, f->stream);
     AD_HIP(hipStreamSynchronize(f->stream));
   });
 }
 
-void ad_transient_destroy(ad_transient* f) { destroy(f); }
+void ad_transient_destroy(ad_transient* f) { destroy_handle(f); }
 
 // ---- ad_deesser -------------------------------------------------------------
 void ad_deesser_default_config(ad_deesser_config* cfg, double sample_rate) {
@@ -494,12 +380,7 @@ void ad_deesser_default_config(ad_deesser_config* cfg, double sample_rate) {
   cfg->filter_order = 2;
 }
 
-int ad_deesser_validate(const ad_deesser_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null de-esser config");
-    validate(*cfg);
-  });
-}
+int ad_deesser_validate(const ad_deesser_config* cfg) { return validate_config(cfg, validate); }
 
 int ad_deesser_derived(const ad_deesser_config* cfg, double* section, double* band_norm, double* threshold_log2,
                        double* knee_width_log2, double* range_lin, double* attack_coeff, double* release_coeff) {
@@ -518,7 +399,8 @@ int ad_deesser_derived(const ad_deesser_config* cfg, double* section, double* ba
 }
 
 int ad_deesser_create(const ad_deesser_config* cfg, int channels, int device, ad_deesser** out) {
-  return create<ad_deesser>(cfg, channels, device, out, +[](ad_deesser* f) {
+  return create_handle(cfg, channels, device, out, validate, [](ad_deesser* f, const ad_deesser_config&) {
+    f->init_env();
     f->d = deesser_derive(f->cfg);
     f->cfg.attack_coeff = f->d.attack;
     f->cfg.release_coeff = f->d.release;
@@ -535,8 +417,7 @@ int ad_deesser_create(const ad_deesser_config* cfg, int channels, int device, ad
 }
 
 int ad_deesser_set_param(ad_deesser* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null de-esser handle");
+  return with_handle(f, [&] {
     ad_deesser_config c = f->cfg;
     bool rebuild = false, times = false;
     switch (which) {
@@ -585,8 +466,7 @@ int ad_deesser_get_config(const ad_deesser* f, ad_deesser_config* cfg) {
 }
 
 int ad_deesser_kernel_info(const ad_deesser* f, int* channels_per_workgroup, int* tile, int* lds_bytes, int* cascades) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null de-esser handle");
+  return with_handle(f, [&] {
     const int mode = deesser_walk_mode(f);
     const bool split = mode == DEESS_SPLIT_ONE || mode == DEESS_SPLIT_TWO;
     const int t = split ? kDynWalkTileMulti : kDynWalkTile;
@@ -635,19 +515,15 @@ int ad_deesser_metrics(ad_deesser* f, int channel, double* detection_level, doub
 
 int ad_deesser_reset_metrics(ad_deesser* f) {
   // ResetMetrics :504-506
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null de-esser handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     deesser_reset_metrics(f);
   });
 }
 
 int ad_deesser_gain(ad_deesser* f, const double* levels, double* gains, int64_t n) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null de-esser handle");
+  return with_handle(f, [&] {
     if (n < 0 || (n > 0 && (!levels || !gains))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad gain buffers");
     if (n == 0) return;
-    DeviceScope ds(f->device);
     f->curve.reserve((size_t)n);
     AD_HIP(hipMemcpyAsync(f->curve.p, levels, (size_t)n * sizeof(double), hipMemcpyHostToDevice, f->stream));
     launch_deesser_gain(f->d.gain, f->curve.p, f->curve.p, n, f->stream);
@@ -660,21 +536,19 @@ int ad_deesser_gain(ad_deesser* f, const double* levels, double* gains, int64_t 
 int ad_deesser_process(ad_deesser* f, double* buf, int64_t n) { return process_host(f, buf, n, deesser_run); }
 
 int ad_deesser_process_device(ad_deesser* f, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return process_dev(f, d_buf, stride, n, stream, deesser_run);
+  return process_device(f, d_buf, stride, n, stream, deesser_run);
 }
 
 int ad_deesser_reset(ad_deesser* f) {
   // Reset :485-496: the envelope, both cascades, the metrics; ordered after the last call
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null de-esser handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
-    AD_HIP(hipMemsetAsync(f->env.p, 0, f->env.n * sizeof(double), f->stream));
+    zero(f->env, f->stream);
     deesser_rebuild(f);
     deesser_reset_metrics(f);
   });
 }
 
-void ad_deesser_destroy(ad_deesser* f) { destroy(f); }
+void ad_deesser_destroy(ad_deesser* f) { destroy_handle(f); }
 
 }  // extern "C"

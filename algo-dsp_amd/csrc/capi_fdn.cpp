@@ -9,9 +9,8 @@
 #include <memory>
 #include <utility>
 
-#include "ad_common.hpp"
-#include "stream_order.hpp"
 #include "fdn_kernels.hpp"
+#include "fx_handle.hpp"
 
 using namespace adsp;
 
@@ -25,8 +24,6 @@ constexpr int kMinLine = 4;                                                     
 constexpr double kMaxLine = 134217728.0;  // 2^27 samples
 
 const double kTwoPi = 2.0 * M_PI;
-
-bool finite(double v) { return std::isfinite(v); }
 
 double* field(ad_fdn_config& c, int which) {
   switch (which) {
@@ -68,16 +65,16 @@ bool derive(const ad_fdn_config& c, Derived& d) {
 
 void validate(const ad_fdn_config& c) {
   // the setters' own checks (:95-186)
-  if (!(c.sample_rate > 0) || !finite(c.sample_rate)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb sample rate must be > 0");
-  if (!(c.wet >= 0) || !finite(c.wet)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb wet must be >= 0");
-  if (!(c.dry >= 0) || !finite(c.dry)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb dry must be >= 0");
-  if (!(c.rt60_seconds > 0) || !finite(c.rt60_seconds)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb RT60 must be > 0");
+  if (!(c.sample_rate > 0) || !is_finite(c.sample_rate)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb sample rate must be > 0");
+  if (!(c.wet >= 0) || !is_finite(c.wet)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb wet must be >= 0");
+  if (!(c.dry >= 0) || !is_finite(c.dry)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb dry must be >= 0");
+  if (!(c.rt60_seconds > 0) || !is_finite(c.rt60_seconds)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb RT60 must be > 0");
   if (!(c.damp >= 0 && c.damp <= 1)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb damp must be in [0,1]");
-  if (!(c.pre_delay_seconds >= 0) || !finite(c.pre_delay_seconds))
+  if (!(c.pre_delay_seconds >= 0) || !is_finite(c.pre_delay_seconds))
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb pre-delay must be >= 0");
-  if (!(c.mod_depth_seconds >= 0) || !finite(c.mod_depth_seconds))
+  if (!(c.mod_depth_seconds >= 0) || !is_finite(c.mod_depth_seconds))
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb mod depth must be >= 0");
-  if (!(c.mod_rate_hz >= 0) || !finite(c.mod_rate_hz)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb mod rate must be >= 0");
+  if (!(c.mod_rate_hz >= 0) || !is_finite(c.mod_rate_hz)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb mod rate must be >= 0");
   Derived d;
   if (!derive(c, d)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fdn reverb: a delay line longer than 2^27 samples");
 }
@@ -89,8 +86,7 @@ void swap_buf(DevBuf<double>& a, DevBuf<double>& b) {
 
 }  // namespace
 
-struct ad_fdn {
-  int device = 0, channels = 0;
+struct ad_fdn : HandleCore {
   ad_fdn_config cfg{};
   Derived d{};
   double fb_gain[kFdnLines] = {};
@@ -99,16 +95,6 @@ struct ad_fdn {
   DevBuf<double> fstate;                // [channels][8]
   DevBuf<double> phase;                 // [2]: lfoPhase, ping-pong (cur = phase[ph_cur])
   int ph_cur = 0;
-  hipStream_t stream = nullptr;  // host-buffer calls, resets
-  StreamOrder order;             // calls may come on any stream
-  DevBuf<double> io;             // host-buffer calls
-  ~ad_fdn() {
-    order.release();
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      (void)lib_stream_destroy(stream);
-    }
-  }
 };
 
 namespace {
@@ -118,10 +104,6 @@ void update_gains(ad_fdn* f) {  // updateFeedbackGains :303-312
     const double delay_seconds = f->d.base[i] / f->cfg.sample_rate;
     f->fb_gain[i] = std::pow(10.0, -3 * delay_seconds / f->cfg.rt60_seconds);
   }
-}
-
-void zero(ad_fdn* f, DevBuf<double>& b) {
-  if (b.p) AD_HIP(hipMemsetAsync(b.p, 0, b.n * sizeof(double), f->stream));
 }
 
 // reconfigureDelays (:274-301) for f->cfg: a line whose length changes is
@@ -140,10 +122,10 @@ void reconfigure(ad_fdn* f, const Derived& nd) {
   for (int i = 0; i <= kFdnLines; ++i) {
     if (!fresh[i].p) continue;
     swap_buf(i < kFdnLines ? f->line[i] : f->pre, fresh[i]);
-    zero(f, i < kFdnLines ? f->line[i] : f->pre);
+    zero(i < kFdnLines ? f->line[i] : f->pre, f->stream);
     (i < kFdnLines ? f->wp[i] : f->pre_wp) = 0;
   }
-  zero(f, f->fstate);
+  zero(f->fstate, f->stream);
   AD_HIP(hipStreamSynchronize(f->stream));
   f->d = nd;
   update_gains(f);
@@ -156,7 +138,7 @@ int block_of(const ad_fdn* f) {  // max(1, P): consecutive samples whose reads s
 int sub_of(const ad_fdn* f) { return std::min(block_of(f), kFdnMaxSub); }
 
 void fdn_run(ad_fdn* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
-  f->order.enter(s);
+  CallScope call(f->order, s);
   FdnArgs a{};
   a.buf = d_buf;
   a.stride = stride;
@@ -190,7 +172,6 @@ void fdn_run(ad_fdn* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s)
   for (int i = 0; i < kFdnLines; ++i) f->wp[i] = (int)((f->wp[i] + n) % f->d.len[i]);
   if (f->d.pre_delay > 0) f->pre_wp = (int)((f->pre_wp + n) % f->d.pre_len);  // written only then (:202-205)
   f->ph_cur ^= 1;
-  f->order.leave(s);
 }
 
 }  // namespace
@@ -210,43 +191,21 @@ void ad_fdn_default_config(ad_fdn_config* cfg, double sample_rate) {
   cfg->mod_rate_hz = 0.1;
 }
 
-int ad_fdn_validate(const ad_fdn_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null fdn reverb config");
-    validate(*cfg);
-  });
-}
+int ad_fdn_validate(const ad_fdn_config* cfg) { return validate_config(cfg, validate); }
 
 int ad_fdn_create(const ad_fdn_config* cfg, int channels, int device, ad_fdn** out) {
-  if (out) *out = nullptr;
-  ad_fdn* raw = nullptr;
-  const int rc = guard([&] {
-    if (!out) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null output handle");
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null fdn reverb config");
-    if (channels <= 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channels must be positive");
-    validate(*cfg);
-    const int dev = pick_device(device);
-    DeviceScope ds(dev);
-    std::unique_ptr<ad_fdn> f(new ad_fdn());
-    f->device = dev;
-    f->channels = channels;
-    f->cfg = *cfg;
-    AD_HIP(lib_stream_create(&f->stream));
-    f->fstate.alloc((size_t)channels * kFdnLines);
+  return create_handle(cfg, channels, device, out, validate, [](ad_fdn* f, const ad_fdn_config& c) {
+    f->fstate.alloc((size_t)f->channels * kFdnLines);
     f->phase.alloc(2);
-    AD_HIP(hipMemsetAsync(f->phase.p, 0, 2 * sizeof(double), f->stream));
+    zero(f->phase, f->stream);
     Derived nd;
-    derive(f->cfg, nd);
-    reconfigure(f.get(), nd);
-    raw = f.release();
+    derive(c, nd);
+    reconfigure(f, nd);
   });
-  if (rc == AD_OK && out) *out = raw;
-  return rc;
 }
 
 int ad_fdn_set_param(ad_fdn* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null fdn reverb handle");
+  return with_handle(f, [&] {
     ad_fdn_config c = f->cfg;
     double* v = field(c, which);
     if (!v) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "unknown fdn reverb parameter");
@@ -256,7 +215,6 @@ int ad_fdn_set_param(ad_fdn* f, int which, double value) {
       case AD_FDN_SAMPLE_RATE:
       case AD_FDN_PRE_DELAY:
       case AD_FDN_MOD_DEPTH: {  // :95-106, :154-175
-        DeviceScope ds(f->device);
         const ad_fdn_config old = f->cfg;
         Derived nd;
         derive(c, nd);
@@ -288,15 +246,13 @@ int ad_fdn_get_config(const ad_fdn* f, ad_fdn_config* cfg) {
 
 int ad_fdn_derived(const ad_fdn* f, double feedback_gain[8], int64_t line_len[8], int64_t* pre_len,
                    double* lfo_phase) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null fdn reverb handle");
+  return with_handle(f, [&] {
     for (int i = 0; i < kFdnLines; ++i) {
       if (feedback_gain) feedback_gain[i] = f->fb_gain[i];
       if (line_len) line_len[i] = f->d.len[i];
     }
     if (pre_len) *pre_len = f->d.pre_len;
     if (lfo_phase) {
-      DeviceScope ds(f->device);
       f->order.wait_host();
       AD_HIP(hipMemcpy(lfo_phase, f->phase.p + f->ph_cur, sizeof(double), hipMemcpyDeviceToHost));
     }
@@ -304,61 +260,33 @@ int ad_fdn_derived(const ad_fdn* f, double feedback_gain[8], int64_t line_len[8]
 }
 
 int ad_fdn_kernel_info(const ad_fdn* f, int* block, int* sub_block, int* lds_bytes) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null fdn reverb handle");
+  return with_handle(f, [&] {
     if (block) *block = block_of(f);
     if (sub_block) *sub_block = sub_of(f);
     if (lds_bytes) *lds_bytes = fdn_lds_bytes(sub_of(f));
   });
 }
 
-int ad_fdn_process(ad_fdn* f, double* buf, int64_t n) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null fdn reverb handle");
-    if (n < 0 || (n > 0 && !buf)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    const size_t count = (size_t)f->channels * n;
-    f->io.reserve(count);
-    AD_HIP(hipMemcpyAsync(f->io.p, buf, count * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    fdn_run(f, f->io.p, n, n, f->stream);
-    AD_HIP(hipMemcpyAsync(buf, f->io.p, count * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    AD_HIP(hipStreamSynchronize(f->stream));
-  });
-}
+int ad_fdn_process(ad_fdn* f, double* buf, int64_t n) { return process_host(f, buf, n, fdn_run); }
 
 int ad_fdn_process_device(ad_fdn* f, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null fdn reverb handle");
-    if (n < 0 || (n > 0 && (!d_buf || stride < n))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer geometry");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    fdn_run(f, d_buf, stride, n, reinterpret_cast<hipStream_t>(stream));
-  });
+  return process_device(f, d_buf, stride, n, stream, fdn_run);
 }
 
 int ad_fdn_reset(ad_fdn* f) {
   // Reset :189-197; ordered after the last call, whatever stream it used
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null fdn reverb handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
-    for (auto& l : f->line) zero(f, l);
-    zero(f, f->pre);
-    zero(f, f->fstate);
-    zero(f, f->phase);
+    for (auto& l : f->line) zero(l, f->stream);
+    zero(f->pre, f->stream);
+    zero(f->fstate, f->stream);
+    zero(f->phase, f->stream);
     AD_HIP(hipStreamSynchronize(f->stream));
     for (int& w : f->wp) w = 0;
     f->pre_wp = 0;
   });
 }
 
-void ad_fdn_destroy(ad_fdn* f) {
-  if (!f) return;
-  (void)guard([&] {
-    DeviceScope ds(f->device);
-    delete f;
-  });
-}
+void ad_fdn_destroy(ad_fdn* f) { destroy_handle(f); }
 
 }  // extern "C"

@@ -40,6 +40,7 @@
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "ad_common.hpp"
@@ -57,109 +58,35 @@ void ck(int rc) {
   if (rc != AD_OK) AD_FAIL(rc, ad_last_error());
 }
 
-struct ChainDel {
-  void operator()(ad_fx_chain* c) const { ad_fx_chain_destroy(c); }
+// An effect handle the graph owns, behind the three calls the graph makes on it.
+struct Owned {
+  void* h = nullptr;
+  int (*process)(void*, double*, int64_t, int64_t, void*) = nullptr;  // in place; null where run() spells the call out
+  int (*reset)(void*) = nullptr;
+  void (*destroy)(void*) = nullptr;
 };
-using ChainPtr = std::unique_ptr<ad_fx_chain, ChainDel>;
 
-struct ConvDel {
-  void operator()(ad_conv* c) const { ad_conv_destroy(c); }
-};
-using ConvPtr = std::unique_ptr<ad_conv, ConvDel>;
-
-struct FdnDel {
-  void operator()(ad_fdn* f) const { ad_fdn_destroy(f); }
-};
-using FdnPtr = std::unique_ptr<ad_fdn, FdnDel>;
-
-struct DelayDel {
-  void operator()(ad_delay* d) const { ad_delay_destroy(d); }
-};
-using DelayPtr = std::unique_ptr<ad_delay, DelayDel>;
-
-struct FlangerDel {
-  void operator()(ad_flanger* f) const { ad_flanger_destroy(f); }
-};
-using FlangerPtr = std::unique_ptr<ad_flanger, FlangerDel>;
-
-struct PhaserDel {
-  void operator()(ad_phaser* f) const { ad_phaser_destroy(f); }
-};
-using PhaserPtr = std::unique_ptr<ad_phaser, PhaserDel>;
-
-struct TremoloDel {
-  void operator()(ad_tremolo* f) const { ad_tremolo_destroy(f); }
-};
-using TremoloPtr = std::unique_ptr<ad_tremolo, TremoloDel>;
-
-struct RingmodDel {
-  void operator()(ad_ringmod* f) const { ad_ringmod_destroy(f); }
-};
-using RingmodPtr = std::unique_ptr<ad_ringmod, RingmodDel>;
-
-struct DistortionDel {
-  void operator()(ad_distortion* f) const { ad_distortion_destroy(f); }
-};
-using DistortionPtr = std::unique_ptr<ad_distortion, DistortionDel>;
-
-struct BitcrusherDel {
-  void operator()(ad_bitcrusher* f) const { ad_bitcrusher_destroy(f); }
-};
-using BitcrusherPtr = std::unique_ptr<ad_bitcrusher, BitcrusherDel>;
-
-struct DeesserDel {
-  void operator()(ad_deesser* f) const { ad_deesser_destroy(f); }
-};
-using DeesserPtr = std::unique_ptr<ad_deesser, DeesserDel>;
-
-struct TransientDel {
-  void operator()(ad_transient* f) const { ad_transient_destroy(f); }
-};
-using TransientPtr = std::unique_ptr<ad_transient, TransientDel>;
-
-struct SpecfreezeDel {
-  void operator()(ad_specfreeze* f) const { ad_specfreeze_destroy(f); }
-};
-using SpecfreezePtr = std::unique_ptr<ad_specfreeze, SpecfreezeDel>;
-
-struct PitchspecDel {
-  void operator()(ad_pitchspec* f) const { ad_pitchspec_destroy(f); }
-};
-using PitchspecPtr = std::unique_ptr<ad_pitchspec, PitchspecDel>;
-
-struct LookaheadDel {
-  void operator()(ad_lookahead* f) const { ad_lookahead_destroy(f); }
-};
-using LookaheadPtr = std::unique_ptr<ad_lookahead, LookaheadDel>;
-
-struct VocoderDel {
-  void operator()(ad_vocoder* f) const { ad_vocoder_destroy(f); }
-};
-using VocoderPtr = std::unique_ptr<ad_vocoder, VocoderDel>;
+// The record of a handle from its typed ABI functions: ad_X_process_device, ad_X_reset, ad_X_destroy.
+template <class H, auto Process, int (*Reset)(H*), void (*Destroy)(H*)>
+Owned own(H* h) {
+  Owned o;
+  o.h = h;
+  if constexpr (std::is_invocable_v<decltype(Process), H*, double*, int64_t, int64_t, void*>)
+    o.process = [](void* p, double* d, int64_t stride, int64_t n, void* s) {
+      return Process(static_cast<H*>(p), d, stride, n, s);
+    };
+  o.reset = [](void* p) { return Reset(static_cast<H*>(p)); };
+  o.destroy = [](void* p) { Destroy(static_cast<H*>(p)); };
+  return o;
+}
 
 struct FxOp {
-  enum Kind {
-    ZERO, COPY, MIX, CHAIN, CONV, FDN, DELAY, FLANGER, PHASER, TREMOLO, RINGMOD, DISTORTION, BITCRUSHER, DEESSER,
-    TRANSIENT, SPECFREEZE, PITCHSPEC, LOOKAHEAD, VOCODER
-  } kind;
-  int dst = -1;                 // buffer id (written; CHAIN and later kinds: read and written in place)
-  std::vector<int> srcs;        // COPY / MIX: buffers read; LOOKAHEAD / VOCODER: the side buffer, if any (read only)
-  ad_fx_chain* chain = nullptr;   // CHAIN
-  ad_conv* conv = nullptr;        // CONV (many-channel convolution reverb)
-  ad_fdn* fdn = nullptr;          // FDN (many-channel FDN reverb)
-  ad_delay* delay = nullptr;      // DELAY (feedback delay, delay-simple)
-  ad_flanger* flanger = nullptr;  // FLANGER
-  ad_phaser* phaser = nullptr;    // PHASER
-  ad_tremolo* tremolo = nullptr;  // TREMOLO
-  ad_ringmod* ringmod = nullptr;  // RINGMOD
-  ad_distortion* distortion = nullptr;  // DISTORTION
-  ad_bitcrusher* bitcrusher = nullptr;  // BITCRUSHER
-  ad_deesser* deesser = nullptr;        // DEESSER
-  ad_transient* transient = nullptr;    // TRANSIENT
-  ad_specfreeze* specfreeze = nullptr;  // SPECFREEZE
-  ad_pitchspec* pitchspec = nullptr;    // PITCHSPEC
-  ad_lookahead* lookahead = nullptr;    // LOOKAHEAD
-  ad_vocoder* vocoder = nullptr;        // VOCODER
+  // CHAIN and later kinds process dst in place (schedule() relies on the order)
+  enum Kind { ZERO, COPY, MIX, CHAIN, HANDLE, LOOKAHEAD, VOCODER } kind;
+  int dst = -1;                  // buffer id (written; CHAIN and later kinds: read and written in place)
+  std::vector<int> srcs;         // COPY / MIX: buffers read; LOOKAHEAD / VOCODER: the side buffer, if any (read only)
+  int handle = -1;               // CHAIN and later kinds: the handle, an index into ad_fx_graph::owned
+  ad_fx_chain* chain = nullptr;  // CHAIN: that handle, typed (schedule() sets its staging)
   // schedule (see schedule()): lane 0 is the caller's stream
   int lane = 0;
   std::vector<int> waits;  // ops on other lanes this op waits for
@@ -184,22 +111,9 @@ struct ad_fx_graph {
   int nbuf = 1;          // buffer 0 = the caller's block
   int out_buf = 0;
   std::vector<FxOp> ops;
-  std::vector<ChainPtr> chains;
-  std::vector<ConvPtr> convs;
-  std::vector<FdnPtr> fdns;
-  std::vector<DelayPtr> delays;
-  std::vector<FlangerPtr> flangers;
-  std::vector<PhaserPtr> phasers;
-  std::vector<TremoloPtr> tremolos;
-  std::vector<RingmodPtr> ringmods;
-  std::vector<DistortionPtr> distortions;
-  std::vector<BitcrusherPtr> bitcrushers;
-  std::vector<DeesserPtr> deessers;
-  std::vector<TransientPtr> transients;
-  std::vector<SpecfreezePtr> specfreezes;
-  std::vector<PitchspecPtr> pitchspecs;
-  std::vector<LookaheadPtr> lookaheads;
-  std::vector<VocoderPtr> vocoders;
+  // Every handle of the graph, chains included, in creation order.  Reset and destroy walk it in that order,
+  // not type by type: the handles are independent, and each reset waits for its own handle's last call.
+  std::vector<Owned> owned;
   DevBuf<double> pool;   // buffers 1..nbuf-1, [nbuf-1][channels][cap]
   int64_t cap = 0;
   DevBuf<double> work;   // host-call staging
@@ -217,22 +131,7 @@ struct ad_fx_graph {
         (void)hipStreamSynchronize(l);
         (void)lib_stream_destroy(l);
       }
-    chains.clear();
-    convs.clear();
-    fdns.clear();
-    delays.clear();
-    flangers.clear();
-    phasers.clear();
-    tremolos.clear();
-    ringmods.clear();
-    distortions.clear();
-    bitcrushers.clear();
-    deessers.clear();
-    transients.clear();
-    specfreezes.clear();
-    pitchspecs.clear();
-    lookaheads.clear();
-    vocoders.clear();
+    for (Owned& o : owned) o.destroy(o.h);
     if (stream) {
       (void)hipStreamSynchronize(stream);
       (void)lib_stream_destroy(stream);
@@ -242,17 +141,29 @@ struct ad_fx_graph {
 
 namespace {
 
-ad_fx_chain* new_chain(ad_fx_graph* g) {
+// an op of `kind` on buffer `buf` for the handle created last
+FxOp handle_op(const ad_fx_graph* g, FxOp::Kind kind, int buf) {
+  FxOp op{kind};
+  op.dst = buf;
+  op.handle = (int)g->owned.size() - 1;
+  return op;
+}
+
+// a new chain and its op on buffer `buf` (not yet in g->ops: the caller sets the chain's stages first)
+FxOp new_chain(ad_fx_graph* g, int buf) {
   ad_fx_chain* c = nullptr;
   ck(ad_fx_chain_create(g->channels, g->device, &c));
-  g->chains.emplace_back(c);
-  return c;
+  g->owned.push_back(own<ad_fx_chain, ad_fx_chain_process_device, ad_fx_chain_reset, ad_fx_chain_destroy>(c));
+  FxOp op = handle_op(g, FxOp::CHAIN, buf);
+  op.chain = c;
+  return op;
 }
 
 void flush(ad_fx_graph* g, Group& gr) {
   if (!gr.open) return;
   if (gr.level() > 0) {
-    ad_fx_chain* c = new_chain(g);
+    const FxOp op = new_chain(g, gr.buf);
+    ad_fx_chain* c = op.chain;
     if (!gr.sections.empty()) ck(ad_fx_chain_set_eq(c, gr.sections.data(), (int)(gr.sections.size() / kSecStride), 0));
     if (gr.dyn) {
       if (gr.dyn->dyn_mode == 0)
@@ -262,9 +173,6 @@ void flush(ad_fx_graph* g, Group& gr) {
                                     gr.dyn->dyn_hold_ms));
     }
     if (gr.verb) ck(ad_fx_chain_set_freeverb(c, gr.verb[0], gr.verb[1], gr.verb[2], gr.verb[3], gr.verb[4]));
-    FxOp op{FxOp::CHAIN};
-    op.dst = gr.buf;
-    op.chain = c;
     g->ops.push_back(op);
   }
   gr = Group{};
@@ -295,6 +203,123 @@ Side side_of(const ad_fx_node* nodes, const ad_fx_node_cfg* cfg, int i) {
   return s;
 }
 
+// ---- the node types that are ops of their own on a handle -----------------------
+// Where node i's config lies (null: it is missing): a field of the node or of ext[i], cfg[i] of the size of
+// the type's structure, or the `config` of a side node's structure there; the reverb-conv node is its own.
+using Source = const void* (*)(const ad_fx_node& d, const ad_fx_node_ext* ext, const ad_fx_node_cfg* cfg, int i);
+template <auto Field>
+const void* in_node(const ad_fx_node& d, const ad_fx_node_ext*, const ad_fx_node_cfg*, int) {
+  return d.*Field;
+}
+template <auto Field>
+const void* in_ext(const ad_fx_node&, const ad_fx_node_ext* ext, const ad_fx_node_cfg*, int i) {
+  return ext ? ext[i].*Field : nullptr;
+}
+template <class Cfg>
+const void* in_cfg(const ad_fx_node&, const ad_fx_node_ext*, const ad_fx_node_cfg* cfg, int i) {
+  return node_cfg<Cfg>(cfg, i);
+}
+template <class Node>
+const void* in_side_cfg(const ad_fx_node&, const ad_fx_node_ext*, const ad_fx_node_cfg* cfg, int i) {
+  const Node* c = node_cfg<Node>(cfg, i);
+  return c ? &c->config : nullptr;
+}
+const void* node_itself(const ad_fx_node& d, const ad_fx_node_ext*, const ad_fx_node_cfg*, int) { return &d; }
+
+template <class Cfg, int (*Validate)(const Cfg*)>
+int valid(const void* cfg) {
+  return Validate(static_cast<const Cfg*>(cfg));
+}
+
+// ad_X_create(cfg, channels, device, out) into g->owned
+template <class H, class Cfg, int (*Create)(const Cfg*, int, int, H**), auto Process, int (*Reset)(H*), void (*Destroy)(H*)>
+void create(ad_fx_graph* g, const void* cfg) {
+  H* h = nullptr;
+  ck(Create(static_cast<const Cfg*>(cfg), g->channels, g->device, &h));
+  g->owned.push_back(own<H, Process, Reset, Destroy>(h));
+}
+
+void create_conv(ad_fx_graph* g, const void* node) {
+  const ad_fx_node& d = *static_cast<const ad_fx_node*>(node);
+  ad_conv* c = nullptr;
+  ck(ad_conv_reverb_multi_create(d.ir, d.ir_len, d.conv_min_order, g->channels, g->device, &c));
+  g->owned.push_back(own<ad_conv, ad_conv_reverb_multi_process_device, ad_conv_reset, ad_conv_destroy>(c));
+  ck(ad_conv_reverb_set_wet_dry(c, d.conv_wet, d.conv_dry));
+}
+
+// One row per node type.  A type the runtime supports has a row here or is one of the structural types
+// (input ... freeverb, which compile() handles itself).  `validate` is there for the types whose config is
+// checked before anything is created; the others' create refuses a bad config.
+struct NodeType {
+  int type;
+  FxOp::Kind kind;
+  Source config;
+  int (*validate)(const void* cfg);
+  void (*create)(ad_fx_graph* g, const void* cfg);
+  const char* missing;  // the error of a node without its config (or, validated, without a valid one of its size)
+};
+const NodeType kNodeTypes[] = {
+    {AD_FXN_CONV_REVERB, FxOp::HANDLE, node_itself, nullptr, create_conv, ""},
+    {AD_FXN_FDN_REVERB, FxOp::HANDLE, in_node<&ad_fx_node::fdn>, nullptr,
+     create<ad_fdn, ad_fdn_config, ad_fdn_create, ad_fdn_process_device, ad_fdn_reset, ad_fdn_destroy>,
+     "fx graph: reverb-fdn node without config"},
+    {AD_FXN_DELAY, FxOp::HANDLE, in_node<&ad_fx_node::delay>, nullptr,
+     create<ad_delay, ad_delay_config, ad_delay_create, ad_delay_process_device, ad_delay_reset, ad_delay_destroy>,
+     "fx graph: delay node without config"},
+    {AD_FXN_FLANGER, FxOp::HANDLE, in_node<&ad_fx_node::flanger>, nullptr,
+     create<ad_flanger, ad_flanger_config, ad_flanger_create, ad_flanger_process_device, ad_flanger_reset,
+            ad_flanger_destroy>,
+     "fx graph: flanger node without config"},
+    {AD_FXN_PHASER, FxOp::HANDLE, in_ext<&ad_fx_node_ext::phaser>, nullptr,
+     create<ad_phaser, ad_phaser_config, ad_phaser_create, ad_phaser_process_device, ad_phaser_reset, ad_phaser_destroy>,
+     "fx graph: phaser node without config"},
+    {AD_FXN_TREMOLO, FxOp::HANDLE, in_ext<&ad_fx_node_ext::tremolo>, nullptr,
+     create<ad_tremolo, ad_tremolo_config, ad_tremolo_create, ad_tremolo_process_device, ad_tremolo_reset,
+            ad_tremolo_destroy>,
+     "fx graph: tremolo node without config"},
+    {AD_FXN_RINGMOD, FxOp::HANDLE, in_ext<&ad_fx_node_ext::ringmod>, nullptr,
+     create<ad_ringmod, ad_ringmod_config, ad_ringmod_create, ad_ringmod_process_device, ad_ringmod_reset,
+            ad_ringmod_destroy>,
+     "fx graph: ringmod node without config"},
+    {AD_FXN_DISTORTION, FxOp::HANDLE, in_cfg<ad_distortion_config>, valid<ad_distortion_config, ad_distortion_validate>,
+     create<ad_distortion, ad_distortion_config, ad_distortion_create, ad_distortion_process_device,
+            ad_distortion_reset, ad_distortion_destroy>,
+     "fx graph: distortion node without a valid config of its size"},
+    {AD_FXN_BITCRUSHER, FxOp::HANDLE, in_cfg<ad_bitcrusher_config>, valid<ad_bitcrusher_config, ad_bitcrusher_validate>,
+     create<ad_bitcrusher, ad_bitcrusher_config, ad_bitcrusher_create, ad_bitcrusher_process_device,
+            ad_bitcrusher_reset, ad_bitcrusher_destroy>,
+     "fx graph: bitcrusher node without a valid config of its size"},
+    {AD_FXN_DEESSER, FxOp::HANDLE, in_cfg<ad_deesser_config>, valid<ad_deesser_config, ad_deesser_validate>,
+     create<ad_deesser, ad_deesser_config, ad_deesser_create, ad_deesser_process_device, ad_deesser_reset,
+            ad_deesser_destroy>,
+     "fx graph: de-esser node without a valid config of its size"},
+    {AD_FXN_TRANSIENT, FxOp::HANDLE, in_cfg<ad_transient_config>, valid<ad_transient_config, ad_transient_validate>,
+     create<ad_transient, ad_transient_config, ad_transient_create, ad_transient_process_device, ad_transient_reset,
+            ad_transient_destroy>,
+     "fx graph: transient shaper node without a valid config of its size"},
+    {AD_FXN_SPECFREEZE, FxOp::HANDLE, in_cfg<ad_specfreeze_config>, valid<ad_specfreeze_config, ad_specfreeze_validate>,
+     create<ad_specfreeze, ad_specfreeze_config, ad_specfreeze_create, ad_specfreeze_process_device,
+            ad_specfreeze_reset, ad_specfreeze_destroy>,
+     "fx graph: spectral freeze node without a valid config of its size"},
+    {AD_FXN_PITCHSPEC, FxOp::HANDLE, in_cfg<ad_pitchspec_config>, valid<ad_pitchspec_config, ad_pitchspec_validate>,
+     create<ad_pitchspec, ad_pitchspec_config, ad_pitchspec_create, ad_pitchspec_process_device, ad_pitchspec_reset,
+            ad_pitchspec_destroy>,
+     "fx graph: spectral pitch shifter node without a valid config of its size"},
+    {AD_FXN_LOOKAHEAD, FxOp::LOOKAHEAD, in_side_cfg<ad_fx_lookahead_node>, valid<ad_lookahead_config, ad_lookahead_validate>,
+     create<ad_lookahead, ad_lookahead_config, ad_lookahead_create, ad_lookahead_process_device, ad_lookahead_reset,
+            ad_lookahead_destroy>,
+     "fx graph: lookahead limiter node without a valid config of its size"},
+    {AD_FXN_VOCODER, FxOp::VOCODER, in_side_cfg<ad_fx_vocoder_node>, valid<ad_vocoder_config, ad_vocoder_validate>,
+     create<ad_vocoder, ad_vocoder_config, ad_vocoder_create, ad_vocoder_process_device, ad_vocoder_reset,
+            ad_vocoder_destroy>,
+     "fx graph: vocoder node without a valid config of its size"},
+};
+const NodeType* node_type(int type) {
+  for (const NodeType& t : kNodeTypes)
+    if (t.type == type) return &t;
+  return nullptr;
+}
+
 void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext, const ad_fx_node_cfg* cfg, int n) {
   if (n < 2 || nodes[0].type != AD_FXN_INPUT) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: node 0 must be the input");
   // consumers of each (node, port)
@@ -302,9 +327,8 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
   int out_node = -1;
   for (int i = 0; i < n; ++i) {
     const ad_fx_node& d = nodes[i];
-    if (d.type < AD_FXN_INPUT || d.type > AD_FXN_VOCODER || (d.type > AD_FXN_RINGMOD && d.type < AD_FXN_DISTORTION) ||
-        (d.type > AD_FXN_BITCRUSHER && d.type < AD_FXN_DEESSER) ||
-        (d.type > AD_FXN_PITCHSPEC && d.type < AD_FXN_LOOKAHEAD))
+    const NodeType* t = node_type(d.type);
+    if (!t && (d.type < AD_FXN_INPUT || d.type > AD_FXN_FREEVERB))
       AD_FAIL(AD_ERR_UNKNOWN_EFFECT, "fx graph: node type not supported by the GPU runtime");
     if (d.type == AD_FXN_INPUT && i != 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: more than one input node");
     if (d.type == AD_FXN_OUTPUT) {
@@ -328,54 +352,9 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
     if (d.type == AD_FXN_COMPRESSOR && !d.comp) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: compressor without config");
     if (d.type == AD_FXN_CONV_REVERB && !d.bypassed && (!d.ir || d.ir_len <= 0))
       AD_FAIL(AD_ERR_EMPTY_IMPULSE_RESPONSE, "fx graph: reverb-conv node without an impulse response");
-    if (d.type == AD_FXN_FDN_REVERB && !d.fdn) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: reverb-fdn node without config");
-    if (d.type == AD_FXN_DELAY && !d.delay) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: delay node without config");
-    if (d.type == AD_FXN_FLANGER && !d.flanger) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: flanger node without config");
-    if (d.type == AD_FXN_PHASER && !(ext && ext[i].phaser))
-      AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: phaser node without config");
-    if (d.type == AD_FXN_TREMOLO && !(ext && ext[i].tremolo))
-      AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: tremolo node without config");
-    if (d.type == AD_FXN_RINGMOD && !(ext && ext[i].ringmod))
-      AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: ringmod node without config");
-    if (d.type == AD_FXN_DISTORTION) {
-      const ad_distortion_config* c = node_cfg<ad_distortion_config>(cfg, i);
-      if (!c || ad_distortion_validate(c) != AD_OK)
-        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: distortion node without a valid config of its size");
-    }
-    if (d.type == AD_FXN_BITCRUSHER) {
-      const ad_bitcrusher_config* c = node_cfg<ad_bitcrusher_config>(cfg, i);
-      if (!c || ad_bitcrusher_validate(c) != AD_OK)
-        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: bitcrusher node without a valid config of its size");
-    }
-    if (d.type == AD_FXN_DEESSER) {
-      const ad_deesser_config* c = node_cfg<ad_deesser_config>(cfg, i);
-      if (!c || ad_deesser_validate(c) != AD_OK)
-        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: de-esser node without a valid config of its size");
-    }
-    if (d.type == AD_FXN_TRANSIENT) {
-      const ad_transient_config* c = node_cfg<ad_transient_config>(cfg, i);
-      if (!c || ad_transient_validate(c) != AD_OK)
-        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: transient shaper node without a valid config of its size");
-    }
-    if (d.type == AD_FXN_SPECFREEZE) {
-      const ad_specfreeze_config* c = node_cfg<ad_specfreeze_config>(cfg, i);
-      if (!c || ad_specfreeze_validate(c) != AD_OK)
-        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: spectral freeze node without a valid config of its size");
-    }
-    if (d.type == AD_FXN_PITCHSPEC) {
-      const ad_pitchspec_config* c = node_cfg<ad_pitchspec_config>(cfg, i);
-      if (!c || ad_pitchspec_validate(c) != AD_OK)
-        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: spectral pitch shifter node without a valid config of its size");
-    }
-    if (d.type == AD_FXN_LOOKAHEAD) {
-      const ad_fx_lookahead_node* c = node_cfg<ad_fx_lookahead_node>(cfg, i);
-      if (!c || ad_lookahead_validate(&c->config) != AD_OK)
-        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: lookahead limiter node without a valid config of its size");
-    }
-    if (d.type == AD_FXN_VOCODER) {
-      const ad_fx_vocoder_node* c = node_cfg<ad_fx_vocoder_node>(cfg, i);
-      if (!c || ad_vocoder_validate(&c->config) != AD_OK)
-        AD_FAIL(AD_ERR_INVALID_ARGUMENT, "fx graph: vocoder node without a valid config of its size");
+    if (t) {
+      const void* c = t->config(d, ext, cfg, i);
+      if (!c || (t->validate && t->validate(c) != AD_OK)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, t->missing);
     }
     // a side consumer counts: a parent it reads is not rewritten in place by that parent's main consumer
     const Side side = side_of(nodes, cfg, i);
@@ -423,195 +402,38 @@ void compile(ad_fx_graph* g, const ad_fx_node* nodes, const ad_fx_node_ext* ext,
       cp.dst = hb;
       cp.srcs.push_back(b);
       g->ops.push_back(cp);
-      FxOp lo{FxOp::CHAIN};
-      lo.dst = b;
-      lo.chain = new_chain(g);
+      const FxOp lo = new_chain(g, b);
       ck(ad_fx_chain_set_eq(lo.chain, d.sections, d.nsec, 0));
       g->ops.push_back(lo);
-      FxOp hi{FxOp::CHAIN};
-      hi.dst = hb;
-      hi.chain = new_chain(g);
+      const FxOp hi = new_chain(g, hb);
       ck(ad_fx_chain_set_eq(hi.chain, d.sections2, d.nsec2, 0));
       g->ops.push_back(hi);
       buf_of[(size_t)i * 2 + 1] = hb;
       continue;
     }
     if (d.type == AD_FXN_OUTPUT || d.type == AD_FXN_PASS || d.bypassed) continue;
-    if (d.type == AD_FXN_CONV_REVERB) {
+    if (const NodeType* t = node_type(d.type)) {  // an op of its own on a new handle
       flush(g, gr);
-      ad_conv* cr = nullptr;
-      ck(ad_conv_reverb_multi_create(d.ir, d.ir_len, d.conv_min_order, g->channels, g->device, &cr));
-      g->convs.emplace_back(cr);
-      ck(ad_conv_reverb_set_wet_dry(cr, d.conv_wet, d.conv_dry));
-      FxOp op{FxOp::CONV};
-      op.dst = b;
-      op.conv = cr;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_FDN_REVERB) {
-      flush(g, gr);
-      ad_fdn* fr = nullptr;
-      ck(ad_fdn_create(d.fdn, g->channels, g->device, &fr));
-      g->fdns.emplace_back(fr);
-      FxOp op{FxOp::FDN};
-      op.dst = b;
-      op.fdn = fr;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_DELAY) {
-      flush(g, gr);
-      ad_delay* dl = nullptr;
-      ck(ad_delay_create(d.delay, g->channels, g->device, &dl));
-      g->delays.emplace_back(dl);
-      FxOp op{FxOp::DELAY};
-      op.dst = b;
-      op.delay = dl;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_FLANGER) {
-      flush(g, gr);
-      ad_flanger* fl = nullptr;
-      ck(ad_flanger_create(d.flanger, g->channels, g->device, &fl));
-      g->flangers.emplace_back(fl);
-      FxOp op{FxOp::FLANGER};
-      op.dst = b;
-      op.flanger = fl;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_PHASER) {
-      flush(g, gr);
-      ad_phaser* ph = nullptr;
-      ck(ad_phaser_create(ext[i].phaser, g->channels, g->device, &ph));
-      g->phasers.emplace_back(ph);
-      FxOp op{FxOp::PHASER};
-      op.dst = b;
-      op.phaser = ph;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_TREMOLO) {
-      flush(g, gr);
-      ad_tremolo* tr = nullptr;
-      ck(ad_tremolo_create(ext[i].tremolo, g->channels, g->device, &tr));
-      g->tremolos.emplace_back(tr);
-      FxOp op{FxOp::TREMOLO};
-      op.dst = b;
-      op.tremolo = tr;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_RINGMOD) {
-      flush(g, gr);
-      ad_ringmod* rm = nullptr;
-      ck(ad_ringmod_create(ext[i].ringmod, g->channels, g->device, &rm));
-      g->ringmods.emplace_back(rm);
-      FxOp op{FxOp::RINGMOD};
-      op.dst = b;
-      op.ringmod = rm;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_DISTORTION) {
-      flush(g, gr);
-      ad_distortion* ds = nullptr;
-      ck(ad_distortion_create(node_cfg<ad_distortion_config>(cfg, i), g->channels, g->device, &ds));
-      g->distortions.emplace_back(ds);
-      FxOp op{FxOp::DISTORTION};
-      op.dst = b;
-      op.distortion = ds;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_BITCRUSHER) {
-      flush(g, gr);
-      ad_bitcrusher* bc = nullptr;
-      ck(ad_bitcrusher_create(node_cfg<ad_bitcrusher_config>(cfg, i), g->channels, g->device, &bc));
-      g->bitcrushers.emplace_back(bc);
-      FxOp op{FxOp::BITCRUSHER};
-      op.dst = b;
-      op.bitcrusher = bc;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_DEESSER) {
-      flush(g, gr);
-      ad_deesser* de = nullptr;
-      ck(ad_deesser_create(node_cfg<ad_deesser_config>(cfg, i), g->channels, g->device, &de));
-      g->deessers.emplace_back(de);
-      FxOp op{FxOp::DEESSER};
-      op.dst = b;
-      op.deesser = de;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_TRANSIENT) {
-      flush(g, gr);
-      ad_transient* ts = nullptr;
-      ck(ad_transient_create(node_cfg<ad_transient_config>(cfg, i), g->channels, g->device, &ts));
-      g->transients.emplace_back(ts);
-      FxOp op{FxOp::TRANSIENT};
-      op.dst = b;
-      op.transient = ts;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_SPECFREEZE) {
-      flush(g, gr);
-      ad_specfreeze* sf = nullptr;
-      ck(ad_specfreeze_create(node_cfg<ad_specfreeze_config>(cfg, i), g->channels, g->device, &sf));
-      g->specfreezes.emplace_back(sf);
-      FxOp op{FxOp::SPECFREEZE};
-      op.dst = b;
-      op.specfreeze = sf;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_PITCHSPEC) {
-      flush(g, gr);
-      ad_pitchspec* ps = nullptr;
-      ck(ad_pitchspec_create(node_cfg<ad_pitchspec_config>(cfg, i), g->channels, g->device, &ps));
-      g->pitchspecs.emplace_back(ps);
-      FxOp op{FxOp::PITCHSPEC};
-      op.dst = b;
-      op.pitchspec = ps;
-      g->ops.push_back(op);
-      continue;
-    }
-    if (d.type == AD_FXN_LOOKAHEAD || d.type == AD_FXN_VOCODER) {
-      flush(g, gr);
-      // the side input (processSidechainNode chain_process.go:249-256): one side parent is read where it
-      // lies, several mix into a buffer of their own; none means the node's own input, which the limiter
-      // takes as "no sidechain" and the vocoder as one pointer for both inputs (a workgroup reads its samples
-      // before it stores them)
-      const Side side = side_of(nodes, cfg, i);
       int sb = -1;
-      if (side.n == 1) {
-        sb = buf_of[(size_t)side.parents[0] * 2 + side.ports[0]];
-      } else if (side.n > 1) {
-        sb = g->nbuf++;
-        FxOp mix{FxOp::MIX};
-        mix.dst = sb;
-        for (int k = 0; k < side.n; ++k) mix.srcs.push_back(buf_of[(size_t)side.parents[k] * 2 + side.ports[k]]);
-        g->ops.push_back(mix);
+      if (t->kind != FxOp::HANDLE) {
+        // the side input (processSidechainNode chain_process.go:249-256): one side parent is read where it
+        // lies, several mix into a buffer of their own; none means the node's own input, which the limiter
+        // takes as "no sidechain" and the vocoder as one pointer for both inputs (a workgroup reads its samples
+        // before it stores them)
+        const Side side = side_of(nodes, cfg, i);
+        if (side.n == 1) {
+          sb = buf_of[(size_t)side.parents[0] * 2 + side.ports[0]];
+        } else if (side.n > 1) {
+          sb = g->nbuf++;
+          FxOp mix{FxOp::MIX};
+          mix.dst = sb;
+          for (int k = 0; k < side.n; ++k) mix.srcs.push_back(buf_of[(size_t)side.parents[k] * 2 + side.ports[k]]);
+          g->ops.push_back(mix);
+        }
       }
-      FxOp op{d.type == AD_FXN_LOOKAHEAD ? FxOp::LOOKAHEAD : FxOp::VOCODER};
-      op.dst = b;
+      t->create(g, t->config(d, ext, cfg, i));
+      FxOp op = handle_op(g, t->kind, b);
       if (sb >= 0) op.srcs.push_back(sb);
-      if (d.type == AD_FXN_LOOKAHEAD) {
-        ad_lookahead* la = nullptr;
-        ck(ad_lookahead_create(&node_cfg<ad_fx_lookahead_node>(cfg, i)->config, g->channels, g->device, &la));
-        g->lookaheads.emplace_back(la);
-        op.lookahead = la;
-      } else {
-        ad_vocoder* vc = nullptr;
-        ck(ad_vocoder_create(&node_cfg<ad_fx_vocoder_node>(cfg, i)->config, g->channels, g->device, &vc));
-        g->vocoders.emplace_back(vc);
-        op.vocoder = vc;
-      }
       g->ops.push_back(op);
       continue;
     }
@@ -743,57 +565,23 @@ void run(ad_fx_graph* g, double* d0, int64_t stride0, int64_t n, hipStream_t s) 
         break;
       }
       case FxOp::CHAIN:
-        ck(ad_fx_chain_process_device(op.chain, dst, st(op.dst), n, ls));
+      case FxOp::HANDLE: {
+        const Owned& o = g->owned[op.handle];
+        ck(o.process(o.h, dst, st(op.dst), n, ls));
         break;
-      case FxOp::CONV:
-        ck(ad_conv_reverb_multi_process_device(op.conv, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::FDN:
-        ck(ad_fdn_process_device(op.fdn, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::DELAY:
-        ck(ad_delay_process_device(op.delay, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::FLANGER:
-        ck(ad_flanger_process_device(op.flanger, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::PHASER:
-        ck(ad_phaser_process_device(op.phaser, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::TREMOLO:
-        ck(ad_tremolo_process_device(op.tremolo, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::RINGMOD:
-        ck(ad_ringmod_process_device(op.ringmod, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::DISTORTION:
-        ck(ad_distortion_process_device(op.distortion, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::BITCRUSHER:
-        ck(ad_bitcrusher_process_device(op.bitcrusher, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::DEESSER:
-        ck(ad_deesser_process_device(op.deesser, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::TRANSIENT:
-        ck(ad_transient_process_device(op.transient, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::SPECFREEZE:
-        ck(ad_specfreeze_process_device(op.specfreeze, dst, st(op.dst), n, ls));
-        break;
-      case FxOp::PITCHSPEC:
-        ck(ad_pitchspec_process_device(op.pitchspec, dst, st(op.dst), n, ls));
-        break;
+      }
       case FxOp::LOOKAHEAD: {
         const bool has = !op.srcs.empty();
-        ck(ad_lookahead_process_device(op.lookahead, dst, st(op.dst), has ? buf_ptr(g, op.srcs[0], d0) : nullptr,
-                                       has ? st(op.srcs[0]) : 0, has ? n : 0, n, ls));
+        ck(ad_lookahead_process_device(static_cast<ad_lookahead*>(g->owned[op.handle].h), dst, st(op.dst),
+                                       has ? buf_ptr(g, op.srcs[0], d0) : nullptr, has ? st(op.srcs[0]) : 0,
+                                       has ? n : 0, n, ls));
         break;
       }
       case FxOp::VOCODER: {
         const bool has = !op.srcs.empty();
-        ck(ad_vocoder_process_device(op.vocoder, dst, st(op.dst), has ? buf_ptr(g, op.srcs[0], d0) : dst,
-                                     has ? st(op.srcs[0]) : st(op.dst), dst, st(op.dst), n, ls));
+        ck(ad_vocoder_process_device(static_cast<ad_vocoder*>(g->owned[op.handle].h), dst, st(op.dst),
+                                     has ? buf_ptr(g, op.srcs[0], d0) : dst, has ? st(op.srcs[0]) : st(op.dst), dst,
+                                     st(op.dst), n, ls));
         break;
       }
     }
@@ -880,22 +668,7 @@ int ad_fx_graph_process(ad_fx_graph* g, double* buf, int64_t n) {
 
 int ad_fx_graph_reset(ad_fx_graph* g) {
   return graph_guard(g, [&] {
-    for (auto& c : g->chains) ck(ad_fx_chain_reset(c.get()));
-    for (auto& c : g->convs) ck(ad_conv_reset(c.get()));
-    for (auto& f : g->fdns) ck(ad_fdn_reset(f.get()));
-    for (auto& d : g->delays) ck(ad_delay_reset(d.get()));
-    for (auto& f : g->flangers) ck(ad_flanger_reset(f.get()));
-    for (auto& f : g->phasers) ck(ad_phaser_reset(f.get()));
-    for (auto& f : g->tremolos) ck(ad_tremolo_reset(f.get()));
-    for (auto& f : g->ringmods) ck(ad_ringmod_reset(f.get()));
-    for (auto& f : g->distortions) ck(ad_distortion_reset(f.get()));
-    for (auto& f : g->bitcrushers) ck(ad_bitcrusher_reset(f.get()));
-    for (auto& f : g->deessers) ck(ad_deesser_reset(f.get()));
-    for (auto& f : g->transients) ck(ad_transient_reset(f.get()));
-    for (auto& f : g->specfreezes) ck(ad_specfreeze_reset(f.get()));
-    for (auto& f : g->pitchspecs) ck(ad_pitchspec_reset(f.get()));
-    for (auto& f : g->lookaheads) ck(ad_lookahead_reset(f.get()));
-    for (auto& f : g->vocoders) ck(ad_vocoder_reset(f.get()));
+    for (const Owned& o : g->owned) ck(o.reset(o.h));
   });
 }
 

@@ -18,24 +18,18 @@
 #include <cmath>
 #include <memory>
 
-#include "ad_common.hpp"
 #include "dynfx_kernels.hpp"
-#include "stream_order.hpp"
+#include "fx_handle.hpp"
 
 using namespace adsp;
 
 namespace {
 
 constexpr double kLog2Of10Div20 = 0.166096404744;    // compressor.go:27 (truncated literal, kept)
-constexpr size_t kScratchBytes = (size_t)256 << 20;  // the scratch rows of one pass: a call longer than this is cut
-constexpr int64_t kMinSegment = 1024;
 constexpr int kScratchRows = 3;  // env_s, prog_s, side_s
 
-bool finite(double v) { return std::isfinite(v); }
-bool in_range(double v, double lo, double hi) { return v >= lo && v <= hi; }  // false for NaN
-
 void validate(const ad_lookahead_config& c) {
-  if (!(c.sample_rate > 0) || !finite(c.sample_rate))
+  if (!(c.sample_rate > 0) || !is_finite(c.sample_rate))
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "lookahead limiter sample rate must be positive and finite");
   if (!in_range(c.threshold_db, -24, 0)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "lookahead limiter threshold must be in [-24, 0]");
   if (!in_range(c.release_ms, 1, 5000)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "lookahead limiter release must be in [1, 5000]");
@@ -62,8 +56,7 @@ Derived derive(const ad_lookahead_config& c) {
 
 }  // namespace
 
-struct ad_lookahead {
-  int device = 0, channels = 0;
+struct ad_lookahead : HandleCore {
   ad_lookahead_config cfg{};
   Derived d{};
   DevBuf<double> env;             // [channels]
@@ -71,16 +64,7 @@ struct ad_lookahead {
   int cur = 0;
   DevBuf<double> env_s, prog_s, side_s;  // [channels][pitch] of one pass
   int64_t last_n = -1, last_pitch = 0;   // the last call, where one pass took it
-  hipStream_t stream = nullptr;   // host-buffer calls, resets
-  StreamOrder order;              // calls may come on any stream
-  DevBuf<double> io, curve;       // host-buffer calls, ad_lookahead_gain
-  ~ad_lookahead() {
-    order.release();
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      (void)lib_stream_destroy(stream);
-    }
-  }
+  DevBuf<double> curve;                  // ad_lookahead_gain
 };
 
 namespace {
@@ -91,7 +75,7 @@ void rebuild_delay(ad_lookahead* f, int64_t delay) {
   const size_t count = (size_t)f->channels * (size_t)delay;
   for (auto& h : f->hist) {
     h.alloc(count);
-    if (count) AD_HIP(hipMemsetAsync(h.p, 0, count * sizeof(double), f->stream));
+    zero(h, f->stream);
   }
   AD_HIP(hipStreamSynchronize(f->stream));
   f->cur = 0;
@@ -99,10 +83,9 @@ void rebuild_delay(ad_lookahead* f, int64_t delay) {
 
 void run(ad_lookahead* f, double* d_buf, int64_t stride, const double* d_side, int64_t side_stride, int64_t side_n,
          int64_t n, hipStream_t s) {
-  f->order.enter(s);
+  CallScope call(f->order, s);
   const int64_t D = f->d.delay, C = f->channels;
-  const int64_t fit = (int64_t)(kScratchBytes / ((size_t)C * kScratchRows * sizeof(double))) - 1;
-  const int64_t seg = std::min(n, std::max(fit, kMinSegment));
+  const int64_t seg = scratch_segment(n, f->channels, kScratchRows);
   f->env_s.reserve((size_t)C * (seg + 1));  // hipFree waits for the device, so no earlier call still reads the old one
   f->prog_s.reserve((size_t)C * seg);
   for (int64_t off = 0; off < n; off += seg) {
@@ -157,7 +140,6 @@ void run(ad_lookahead* f, double* d_buf, int64_t stride, const double* d_side, i
   AD_HIP(hipGetLastError());
   f->last_n = n <= seg ? n : -1;
   f->last_pitch = seg + 1;
-  f->order.leave(s);
 }
 
 }  // namespace
@@ -173,12 +155,7 @@ void ad_lookahead_default_config(ad_lookahead_config* cfg, double sample_rate) {
   cfg->lookahead_ms = 3.0;
 }
 
-int ad_lookahead_validate(const ad_lookahead_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null lookahead limiter config");
-    validate(*cfg);
-  });
-}
+int ad_lookahead_validate(const ad_lookahead_config* cfg) { return validate_config(cfg, validate); }
 
 int ad_lookahead_derived(const ad_lookahead_config* cfg, double* attack_coeff, double* release_coeff,
                          double* threshold_log2, int64_t* delay_samples) {
@@ -194,33 +171,16 @@ int ad_lookahead_derived(const ad_lookahead_config* cfg, double* attack_coeff, d
 }
 
 int ad_lookahead_create(const ad_lookahead_config* cfg, int channels, int device, ad_lookahead** out) {
-  if (out) *out = nullptr;
-  ad_lookahead* raw = nullptr;
-  const int rc = guard([&] {
-    if (!out) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null output handle");
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null config");
-    if (channels <= 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channels must be positive");
-    validate(*cfg);
-    const int dev = pick_device(device);
-    DeviceScope ds(dev);
-    std::unique_ptr<ad_lookahead> f(new ad_lookahead());
-    f->device = dev;
-    f->channels = channels;
-    f->cfg = *cfg;
-    f->d = derive(*cfg);
-    AD_HIP(lib_stream_create(&f->stream));
-    f->env.alloc((size_t)channels);
-    AD_HIP(hipMemsetAsync(f->env.p, 0, f->env.n * sizeof(double), f->stream));
-    rebuild_delay(f.get(), f->d.delay);
-    raw = f.release();
+  return create_handle(cfg, channels, device, out, validate, [](ad_lookahead* f, const ad_lookahead_config& c) {
+    f->d = derive(c);
+    f->env.alloc((size_t)f->channels);
+    zero(f->env, f->stream);
+    rebuild_delay(f, f->d.delay);
   });
-  if (rc == AD_OK && out) *out = raw;
-  return rc;
 }
 
 int ad_lookahead_set_param(ad_lookahead* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null lookahead limiter handle");
+  return with_handle(f, [&] {
     ad_lookahead_config c = f->cfg;
     switch (which) {
       case AD_LOOKAHEAD_SAMPLE_RATE: c.sample_rate = value; break;  // SetSampleRate :146-161
@@ -231,10 +191,7 @@ int ad_lookahead_set_param(ad_lookahead* f, int which, double value) {
     }
     validate(c);  // every other field is valid already: the setter's own check
     const Derived d = derive(c);
-    if (which == AD_LOOKAHEAD_SAMPLE_RATE || which == AD_LOOKAHEAD_LOOKAHEAD) {
-      DeviceScope ds(f->device);
-      rebuild_delay(f, d.delay);
-    }
+    if (which == AD_LOOKAHEAD_SAMPLE_RATE || which == AD_LOOKAHEAD_LOOKAHEAD) rebuild_delay(f, d.delay);
     f->cfg = c;
     f->d = d;
   });
@@ -249,8 +206,8 @@ int ad_lookahead_get_config(const ad_lookahead* f, ad_lookahead_config* cfg) {
 
 int ad_lookahead_get_state(ad_lookahead* f, int channel, double* envelope) {
   return guard([&] {
-    if (!f || !envelope) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null lookahead limiter handle or output");
-    if (channel < 0 || channel >= f->channels) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channel out of range");
+    check_channel(f, channel);
+    if (!envelope) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null state output");
     DeviceScope ds(f->device);
     f->order.wait_host();
     AD_HIP(hipMemcpy(envelope, f->env.p + channel, sizeof(double), hipMemcpyDeviceToHost));
@@ -258,11 +215,9 @@ int ad_lookahead_get_state(ad_lookahead* f, int channel, double* envelope) {
 }
 
 int ad_lookahead_gain(ad_lookahead* f, const double* levels, double* gains, int64_t n) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null lookahead limiter handle");
+  return with_handle(f, [&] {
     if (n < 0 || (n > 0 && (!levels || !gains))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad gain buffers");
     if (n == 0) return;
-    DeviceScope ds(f->device);
     f->curve.reserve((size_t)n);
     AD_HIP(hipMemcpyAsync(f->curve.p, levels, (size_t)n * sizeof(double), hipMemcpyHostToDevice, f->stream));
     launch_deesser_gain(f->d.gain, f->curve.p, f->curve.p, n, f->stream);
@@ -285,11 +240,9 @@ int ad_lookahead_last_envelope(ad_lookahead* f, double* envelope, int64_t n) {
 }
 
 int ad_lookahead_process(ad_lookahead* f, double* program, const double* sidechain, int64_t side_n, int64_t n) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null lookahead limiter handle");
+  return with_handle(f, [&] {
     if (n < 0 || (n > 0 && !program) || side_n < 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer");
     if (n == 0) return;
-    DeviceScope ds(f->device);
     const size_t count = (size_t)f->channels * n, side_count = sidechain ? (size_t)f->channels * side_n : 0;
     f->order.wait_host();
     f->io.reserve(count + side_count + 1);
@@ -308,8 +261,7 @@ int ad_lookahead_process(ad_lookahead* f, double* program, const double* sidecha
 
 int ad_lookahead_process_device(ad_lookahead* f, double* d_buf, int64_t stride, const double* d_side, int64_t side_stride,
                                 int64_t side_n, int64_t n, void* stream) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null lookahead limiter handle");
+  return with_handle(f, [&] {
     if (n < 0 || (n > 0 && (!d_buf || stride < n))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer geometry");
     if (d_side && (side_n < 0 || side_stride < side_n)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad sidechain geometry");
     if (n == 0) return;
@@ -319,28 +271,19 @@ int ad_lookahead_process_device(ad_lookahead* f, double* d_buf, int64_t stride, 
       if (d_buf < b_end && d_side < a_end)
         AD_FAIL(AD_ERR_INVALID_ARGUMENT, "lookahead limiter: the sidechain rows overlap the program rows");
     }
-    DeviceScope ds(f->device);
     run(f, d_buf, stride, d_side, side_stride, side_n, n, reinterpret_cast<hipStream_t>(stream));
   });
 }
 
 int ad_lookahead_reset(ad_lookahead* f) {
   // Reset :176-183: the core's envelope and the delay line; ordered after the last call
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null lookahead limiter handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
-    AD_HIP(hipMemsetAsync(f->env.p, 0, f->env.n * sizeof(double), f->stream));
+    zero(f->env, f->stream);
     rebuild_delay(f, f->d.delay);
   });
 }
 
-void ad_lookahead_destroy(ad_lookahead* f) {
-  if (!f) return;
-  (void)guard([&] {
-    DeviceScope ds(f->device);
-    delete f;
-  });
-}
+void ad_lookahead_destroy(ad_lookahead* f) { destroy_handle(f); }
 
 }  // extern "C"

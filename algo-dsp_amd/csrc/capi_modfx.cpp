@@ -13,8 +13,7 @@
 #include <cstring>
 #include <memory>
 
-#include "ad_common.hpp"
-#include "stream_order.hpp"
+#include "fx_handle.hpp"
 #include "modfx_kernels.hpp"
 
 using namespace adsp;
@@ -24,15 +23,11 @@ namespace {
 const double kTwoPi = 2.0 * M_PI;
 constexpr double kNyquistSafety = 0.49;  // phaserNyquistSafetyRatio phaser.go:16
 
-bool finite(double v) { return std::isfinite(v); }
-bool positive(double v) { return v > 0 && finite(v); }
-bool in_range(double v, double lo, double hi) { return v >= lo && v <= hi; }  // false for NaN
-
 void validate(const ad_phaser_config& c) {  // validateParams phaser.go:323-358
   if (!positive(c.sample_rate)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "phaser sample rate must be > 0 and finite");
   if (!positive(c.rate_hz)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "phaser rate must be > 0 and finite");
   if (!positive(c.min_freq_hz)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "phaser min frequency must be > 0 and finite");
-  if (!(c.max_freq_hz > c.min_freq_hz) || !finite(c.max_freq_hz))
+  if (!(c.max_freq_hz > c.min_freq_hz) || !is_finite(c.max_freq_hz))
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "phaser max frequency must be > min frequency and finite");
   if (c.max_freq_hz >= kNyquistSafety * c.sample_rate)
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "phaser max frequency must be < 0.49 of the sample rate");
@@ -45,7 +40,7 @@ void validate(const ad_tremolo_config& c) {  // validateParams tremolo.go:249-27
   if (!positive(c.sample_rate)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "tremolo sample rate must be > 0 and finite");
   if (!positive(c.rate_hz)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "tremolo rate must be > 0 and finite");
   if (!in_range(c.depth, 0, 1)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "tremolo depth must be in [0, 1]");
-  if (!(c.smoothing_ms >= 0) || !finite(c.smoothing_ms))
+  if (!(c.smoothing_ms >= 0) || !is_finite(c.smoothing_ms))
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "tremolo smoothing must be >= 0 and finite");
   if (!in_range(c.mix, 0, 1)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "tremolo mix must be in [0, 1]");
   if (!in_range(c.smoothing_coeff, 0, 1))
@@ -77,49 +72,16 @@ double step_phases(double phase, double inc, double* out, int64_t n) {
   return phase;
 }
 
-// What the three handles share: the phase, the call's tables and the streams.
-struct ModCore {
-  int device = 0, channels = 0;
-  double phase = 0;           // lfoPhase / phase before the next sample
-  DevBuf<double> ph, tab;     // the call's phases, and what the kernels take from them
-  double* host = nullptr;     // pinned; reused once up_ev has passed
-  size_t host_cap = 0;
-  hipEvent_t up_ev = nullptr;
-  bool up_pending = false;
-  hipStream_t stream = nullptr;  // host-buffer calls, resets, peeks
-  StreamOrder order;             // calls may come on any stream
-  DevBuf<double> io;             // host-buffer calls
-  ~ModCore() {
-    order.release();
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      (void)lib_stream_destroy(stream);
-    }
-    if (up_ev) {
-      (void)hipEventSynchronize(up_ev);
-      (void)hipEventDestroy(up_ev);
-    }
-    if (host) (void)hipHostFree(host);
-  }
+// What the three handles share: the phase and the call's tables.
+struct ModCore : HandleCore {
+  double phase = 0;    // lfoPhase / phase before the next sample
+  PinnedUpload ph;     // the call's phases
+  DevBuf<double> tab;  // what the kernels take from them
   // the phases of the next n samples into ph on s; returns the phase after them
   double upload(double inc, int64_t n, hipStream_t s) {
-    if (up_pending) AD_HIP(hipEventSynchronize(up_ev));
-    up_pending = false;
-    if ((size_t)n > host_cap) {
-      if (host) AD_HIP(hipHostFree(host));
-      host = nullptr;
-      host_cap = 0;
-      const size_t cap = std::max<size_t>((size_t)n, 4096);
-      AD_HIP(hipHostMalloc(reinterpret_cast<void**>(&host), cap * sizeof(double), hipHostMallocDefault));
-      host_cap = cap;
-      ph.reserve(cap);  // hipFree waits for the device, so no earlier call still reads the old ones
-      tab.reserve(cap);
-    }
-    const double end = step_phases(phase, inc, host, n);
-    AD_HIP(hipMemcpyAsync(ph.p, host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-    if (!up_ev) AD_HIP(hipEventCreateWithFlags(&up_ev, hipEventDisableTiming));
-    AD_HIP(hipEventRecord(up_ev, s));
-    up_pending = true;
+    const double end = step_phases(phase, inc, ph.stage((size_t)n), n);
+    tab.reserve(ph.cap);  // hipFree waits for the device, so no earlier call still reads the old one
+    ph.send((size_t)n, s);
     return end;
   }
 };
@@ -149,7 +111,7 @@ double lfo_inc(double rate_hz, double fs) { return kTwoPi * rate_hz / fs; }
 // ---- the device work of a call: the table from the uploaded phases ----------
 void phaser_table(ad_phaser* f, int64_t n, hipStream_t s) {
   ModTableArgs t{};
-  t.phase = f->ph.p;
+  t.phase = f->ph.dev.p;
   t.out = f->tab.p;
   t.n = n;
   t.kind = MOD_COEF;
@@ -163,7 +125,7 @@ void phaser_table(ad_phaser* f, int64_t n, hipStream_t s) {
 
 void tremolo_table(ad_tremolo* f, int64_t n, bool commit, hipStream_t s) {
   ModTableArgs t{};
-  t.phase = f->ph.p;
+  t.phase = f->ph.dev.p;
   t.out = f->tab.p;
   t.n = n;
   t.kind = MOD_TARGET;
@@ -178,7 +140,7 @@ void tremolo_table(ad_tremolo* f, int64_t n, bool commit, hipStream_t s) {
 
 void ringmod_table(ad_ringmod* f, int64_t n, hipStream_t s) {
   ModTableArgs t{};
-  t.phase = f->ph.p;
+  t.phase = f->ph.dev.p;
   t.out = f->tab.p;
   t.n = n;
   t.kind = MOD_CARRIER;
@@ -198,7 +160,7 @@ void apply(ModCore* f, double* d_buf, int64_t stride, int64_t n, double mix, hip
 }
 
 void phaser_run(ad_phaser* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
-  f->order.enter(s);
+  CallScope call(f->order, s);
   const double end = f->upload(lfo_inc(f->cfg.rate_hz, f->cfg.sample_rate), n, s);
   phaser_table(f, n, s);
   PhaserArgs a{};
@@ -216,111 +178,45 @@ void phaser_run(ad_phaser* f, double* d_buf, int64_t stride, int64_t n, hipStrea
   launch_phaser(a, s);
   AD_HIP(hipGetLastError());
   f->phase = end;
-  f->order.leave(s);
 }
 
 void tremolo_run(ad_tremolo* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
-  f->order.enter(s);
+  CallScope call(f->order, s);
   const double end = f->upload(lfo_inc(f->cfg.rate_hz, f->cfg.sample_rate), n, s);
   tremolo_table(f, n, true, s);
   apply(f, d_buf, stride, n, f->cfg.mix, s);
   AD_HIP(hipGetLastError());
   f->phase = end;
-  f->order.leave(s);
 }
 
 void ringmod_run(ad_ringmod* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
-  f->order.enter(s);
+  CallScope call(f->order, s);
   const double end = f->upload(f->inc, n, s);
   ringmod_table(f, n, s);
   apply(f, d_buf, stride, n, f->cfg.mix, s);
   AD_HIP(hipGetLastError());
   f->phase = end;
-  f->order.leave(s);
-}
-
-// ---- what the three ABIs share ----------------------------------------------
-template <class H, class Cfg>
-int create(const Cfg* cfg, int channels, int device, H** out, void (*init)(H*)) {
-  if (out) *out = nullptr;
-  H* raw = nullptr;
-  const int rc = guard([&] {
-    if (!out) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null output handle");
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null config");
-    if (channels <= 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channels must be positive");
-    validate(*cfg);
-    const int dev = pick_device(device);
-    DeviceScope ds(dev);
-    std::unique_ptr<H> f(new H());
-    f->device = dev;
-    f->channels = channels;
-    f->cfg = *cfg;
-    AD_HIP(lib_stream_create(&f->stream));
-    init(f.get());
-    AD_HIP(hipStreamSynchronize(f->stream));
-    raw = f.release();
-  });
-  if (rc == AD_OK && out) *out = raw;
-  return rc;
-}
-
-template <class H, class Run>
-int process_host(H* f, double* buf, int64_t n, Run run) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || (n > 0 && !buf)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    const size_t count = (size_t)f->channels * n;
-    f->io.reserve(count);
-    AD_HIP(hipMemcpyAsync(f->io.p, buf, count * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    run(f, f->io.p, n, n, f->stream);
-    AD_HIP(hipMemcpyAsync(buf, f->io.p, count * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    AD_HIP(hipStreamSynchronize(f->stream));
-  });
-}
-
-template <class H, class Run>
-int process_dev(H* f, double* d_buf, int64_t stride, int64_t n, void* stream, Run run) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || (n > 0 && (!d_buf || stride < n))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer geometry");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    run(f, d_buf, stride, n, reinterpret_cast<hipStream_t>(stream));
-  });
 }
 
 // The next n phases and table values, by the code a call runs; nothing advances.
 template <class H, class Table>
 int peek(H* f, int64_t n, double inc, double* phase_out, double* second_out, Table table) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null handle");
+  return with_handle(f, [&] {
     if (n < 0 || (n > 0 && (!phase_out || !second_out))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad peek buffers");
     if (n == 0) return;
-    DeviceScope ds(f->device);
     f->order.wait_host();
     (void)f->upload(inc, n, f->stream);
     table(f, n, f->stream);
     AD_HIP(hipGetLastError());
     AD_HIP(hipMemcpyAsync(second_out, f->tab.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, f->stream));
     AD_HIP(hipStreamSynchronize(f->stream));
-    std::memcpy(phase_out, f->host, (size_t)n * sizeof(double));
-  });
-}
-
-template <class H>
-void destroy(H* f) {
-  if (!f) return;
-  (void)guard([&] {
-    DeviceScope ds(f->device);
-    delete f;
+    std::memcpy(phase_out, f->ph.host, (size_t)n * sizeof(double));
   });
 }
 
 void phaser_clear_stages(ad_phaser* f) {
   f->order.wait_host();
-  AD_HIP(hipMemsetAsync(f->stage.p, 0, f->stage.n * sizeof(double), f->stream));
+  zero(f->stage, f->stream);
   AD_HIP(hipStreamSynchronize(f->stream));
 }
 
@@ -333,10 +229,7 @@ void tremolo_set_cur(ad_tremolo* f, double v) {
 void phaser_commit(ad_phaser* f, const ad_phaser_config& c) {
   validate(c);
   const bool restage = c.stages != f->cfg.stages;  // SetStages :226-230: the same count keeps the states
-  if (restage) {
-    DeviceScope ds(f->device);
-    phaser_clear_stages(f);
-  }
+  if (restage) phaser_clear_stages(f);
   f->cfg = c;
 }
 
@@ -357,25 +250,19 @@ void ad_phaser_default_config(ad_phaser_config* cfg, double sample_rate) {
   cfg->stages = 6;
 }
 
-int ad_phaser_validate(const ad_phaser_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null phaser config");
-    validate(*cfg);
-  });
-}
+int ad_phaser_validate(const ad_phaser_config* cfg) { return validate_config(cfg, validate); }
 
 int ad_phaser_create(const ad_phaser_config* cfg, int channels, int device, ad_phaser** out) {
-  return create<ad_phaser>(cfg, channels, device, out, +[](ad_phaser* f) {
+  return create_handle(cfg, channels, device, out, validate, [](ad_phaser* f, const ad_phaser_config&) {
     f->stage.alloc((size_t)f->channels * 2 * kPhaserMaxStages);
     f->fb.alloc((size_t)f->channels);
-    AD_HIP(hipMemsetAsync(f->stage.p, 0, f->stage.n * sizeof(double), f->stream));
-    AD_HIP(hipMemsetAsync(f->fb.p, 0, f->fb.n * sizeof(double), f->stream));
+    zero(f->stage, f->stream);
+    zero(f->fb, f->stream);
   });
 }
 
 int ad_phaser_set_param(ad_phaser* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null phaser handle");
+  return with_handle(f, [&] {
     ad_phaser_config c = f->cfg;
     switch (which) {
       case AD_PHASER_SAMPLE_RATE: c.sample_rate = value; break;  // SetSampleRate :183-191
@@ -398,8 +285,7 @@ int ad_phaser_set_param(ad_phaser* f, int which, double value) {
 }
 
 int ad_phaser_set_range(ad_phaser* f, double min_freq_hz, double max_freq_hz) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null phaser handle");
+  return with_handle(f, [&] {
     ad_phaser_config c = f->cfg;
     c.min_freq_hz = min_freq_hz;
     c.max_freq_hz = max_freq_hz;
@@ -415,8 +301,7 @@ int ad_phaser_get_config(const ad_phaser* f, ad_phaser_config* cfg) {
 }
 
 int ad_phaser_kernel_info(const ad_phaser* f, int* channels_per_workgroup, int* tile, int* lds_bytes) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null phaser handle");
+  return with_handle(f, [&] {
     if (channels_per_workgroup) *channels_per_workgroup = 64;
     if (tile) *tile = kPhaserTile;
     if (lds_bytes) *lds_bytes = (2 * 64 * kPhaserPitch + kPhaserTile) * (int)sizeof(double);
@@ -430,23 +315,21 @@ int ad_phaser_peek_lfo(ad_phaser* f, int64_t n, double* phase_out, double* coef_
 int ad_phaser_process(ad_phaser* f, double* buf, int64_t n) { return process_host(f, buf, n, phaser_run); }
 
 int ad_phaser_process_device(ad_phaser* f, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return process_dev(f, d_buf, stride, n, stream, phaser_run);
+  return process_device(f, d_buf, stride, n, stream, phaser_run);
 }
 
 int ad_phaser_reset(ad_phaser* f) {
   // Reset :258-265: the stages, feedbackSample and lfoPhase; ordered after the last call
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null phaser handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
-    AD_HIP(hipMemsetAsync(f->stage.p, 0, f->stage.n * sizeof(double), f->stream));
-    AD_HIP(hipMemsetAsync(f->fb.p, 0, f->fb.n * sizeof(double), f->stream));
+    zero(f->stage, f->stream);
+    zero(f->fb, f->stream);
     AD_HIP(hipStreamSynchronize(f->stream));
     f->phase = 0;
   });
 }
 
-void ad_phaser_destroy(ad_phaser* f) { destroy(f); }
+void ad_phaser_destroy(ad_phaser* f) { destroy_handle(f); }
 
 // ---- ad_tremolo -------------------------------------------------------------
 void ad_tremolo_default_config(ad_tremolo_config* cfg, double sample_rate) {
@@ -459,15 +342,10 @@ void ad_tremolo_default_config(ad_tremolo_config* cfg, double sample_rate) {
   cfg->mix = 1.0;
 }
 
-int ad_tremolo_validate(const ad_tremolo_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null tremolo config");
-    validate(*cfg);
-  });
-}
+int ad_tremolo_validate(const ad_tremolo_config* cfg) { return validate_config(cfg, validate); }
 
 int ad_tremolo_create(const ad_tremolo_config* cfg, int channels, int device, ad_tremolo** out) {
-  return create<ad_tremolo>(cfg, channels, device, out, +[](ad_tremolo* f) {
+  return create_handle(cfg, channels, device, out, validate, [](ad_tremolo* f, const ad_tremolo_config&) {
     if (f->cfg.smoothing_coeff == 0) f->cfg.smoothing_coeff = smoothing_coeff(f->cfg.smoothing_ms, f->cfg.sample_rate);
     f->cur.alloc(1);
     tremolo_set_cur(f, 1.0);  // NewTremolo :124
@@ -475,8 +353,7 @@ int ad_tremolo_create(const ad_tremolo_config* cfg, int channels, int device, ad
 }
 
 int ad_tremolo_set_param(ad_tremolo* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null tremolo handle");
+  return with_handle(f, [&] {
     ad_tremolo_config c = f->cfg;
     switch (which) {
       case AD_TREMOLO_SAMPLE_RATE: c.sample_rate = value; break;    // SetSampleRate :138-147
@@ -505,8 +382,7 @@ int ad_tremolo_get_config(const ad_tremolo* f, ad_tremolo_config* cfg) {
 }
 
 int ad_tremolo_kernel_info(const ad_tremolo* f, int* samples_per_workgroup, int* smooth_chunk, int* smoothed) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null tremolo handle");
+  return with_handle(f, [&] {
     if (samples_per_workgroup) *samples_per_workgroup = 2 * kModApplyThreads * kModApplySteps;
     if (smooth_chunk) *smooth_chunk = kModSmoothChunk;
     if (smoothed) *smoothed = f->cfg.smoothing_coeff < 1 ? 1 : 0;
@@ -521,20 +397,18 @@ int ad_tremolo_peek_lfo(ad_tremolo* f, int64_t n, double* phase_out, double* gai
 int ad_tremolo_process(ad_tremolo* f, double* buf, int64_t n) { return process_host(f, buf, n, tremolo_run); }
 
 int ad_tremolo_process_device(ad_tremolo* f, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return process_dev(f, d_buf, stride, n, stream, tremolo_run);
+  return process_device(f, d_buf, stride, n, stream, tremolo_run);
 }
 
 int ad_tremolo_reset(ad_tremolo* f) {
   // Reset :195-198: lfoPhase = 0, currentMod = 1
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null tremolo handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     tremolo_set_cur(f, 1.0);
     f->phase = 0;
   });
 }
 
-void ad_tremolo_destroy(ad_tremolo* f) { destroy(f); }
+void ad_tremolo_destroy(ad_tremolo* f) { destroy_handle(f); }
 
 // ---- ad_ringmod -------------------------------------------------------------
 void ad_ringmod_default_config(ad_ringmod_config* cfg, double sample_rate) {
@@ -544,21 +418,16 @@ void ad_ringmod_default_config(ad_ringmod_config* cfg, double sample_rate) {
   cfg->mix = 1.0;
 }
 
-int ad_ringmod_validate(const ad_ringmod_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null ring modulator config");
-    validate(*cfg);
+int ad_ringmod_validate(const ad_ringmod_config* cfg) { return validate_config(cfg, validate); }
+
+int ad_ringmod_create(const ad_ringmod_config* cfg, int channels, int device, ad_ringmod** out) {
+  return create_handle(cfg, channels, device, out, validate, [](ad_ringmod* f, const ad_ringmod_config& c) {
+    f->inc = lfo_inc(c.carrier_hz, c.sample_rate);
   });
 }
 
-int ad_ringmod_create(const ad_ringmod_config* cfg, int channels, int device, ad_ringmod** out) {
-  return create<ad_ringmod>(cfg, channels, device, out,
-                            +[](ad_ringmod* f) { f->inc = lfo_inc(f->cfg.carrier_hz, f->cfg.sample_rate); });
-}
-
 int ad_ringmod_set_param(ad_ringmod* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null ring modulator handle");
+  return with_handle(f, [&] {
     ad_ringmod_config c = f->cfg;
     switch (which) {
       case AD_RINGMOD_SAMPLE_RATE: c.sample_rate = value; break;  // SetSampleRate :103-112
@@ -580,8 +449,7 @@ int ad_ringmod_get_config(const ad_ringmod* f, ad_ringmod_config* cfg) {
 }
 
 int ad_ringmod_kernel_info(const ad_ringmod* f, int* samples_per_workgroup, int* table_threads, double* phase_inc) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null ring modulator handle");
+  return with_handle(f, [&] {
     if (samples_per_workgroup) *samples_per_workgroup = 2 * kModApplyThreads * kModApplySteps;
     if (table_threads) *table_threads = kModTableThreads;
     if (phase_inc) *phase_inc = f->inc;
@@ -595,17 +463,16 @@ int ad_ringmod_peek_lfo(ad_ringmod* f, int64_t n, double* phase_out, double* car
 int ad_ringmod_process(ad_ringmod* f, double* buf, int64_t n) { return process_host(f, buf, n, ringmod_run); }
 
 int ad_ringmod_process_device(ad_ringmod* f, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return process_dev(f, d_buf, stride, n, stream, ringmod_run);
+  return process_device(f, d_buf, stride, n, stream, ringmod_run);
 }
 
 int ad_ringmod_reset(ad_ringmod* f) {
   // Reset :138-140; ordered after the last call, which took its phases when it was enqueued
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null ring modulator handle");
+  return with_handle(f, [&] {
     f->phase = 0;
   });
 }
 
-void ad_ringmod_destroy(ad_ringmod* f) { destroy(f); }
+void ad_ringmod_destroy(ad_ringmod* f) { destroy_handle(f); }
 
 }  // extern "C"

@@ -22,8 +22,7 @@
 #include <memory>
 #include <vector>
 
-#include "ad_common.hpp"
-#include "stream_order.hpp"
+#include "fx_handle.hpp"
 #include "xover_kernels.hpp"
 
 using namespace adsp;
@@ -35,8 +34,6 @@ constexpr double kMinCrossoverFrequency = 20.0;               // multiband.go:17
 constexpr size_t kScratchBytes = (size_t)2 << 30;             // the band planes of one pass (DESIGN §4i's figure)
 constexpr int64_t kMinChunk = 64;
 
-bool finite(double v) { return std::isfinite(v); }
-
 // ---- design ---------------------------------------------------------------
 struct Sec {
   double c[5];  // b0, b1, b2, a1, a2
@@ -44,7 +41,7 @@ struct Sec {
 const Sec kZero{{0, 0, 0, 0, 0}};
 
 Sec norm(double b0, double b1, double b2, double a0, double a1, double a2) {  // normalizeBiquad design.go:214-223
-  if (a0 == 0 || !finite(a0)) return kZero;
+  if (a0 == 0 || !is_finite(a0)) return kZero;
   return Sec{{b0 / a0, b1 / a0, b2 / a0, a1 / a0, a2 / a0}};
 }
 
@@ -98,7 +95,7 @@ void validate_xover(const double* freqs, int nfreq, int order, double fs) {
   if (nfreq > kXoverMaxStages) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "crossover: at most 7 frequencies");
   if (order <= 0 || order % 2 != 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "crossover: order must be a positive even integer");
   if (order > kMaxOrder) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "crossover: order must be at most 24");
-  if (!(fs > 0) || !finite(fs)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "crossover: sample rate must be positive and finite");
+  if (!(fs > 0) || !is_finite(fs)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "crossover: sample rate must be positive and finite");
   for (int i = 0; i < nfreq; ++i) {
     if (!(freqs[i] > 0 && freqs[i] < fs / 2)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "crossover: frequency must be in (0, fs/2)");
     if (i > 0 && !(freqs[i] > freqs[i - 1])) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "crossover: frequencies must be strictly ascending");
@@ -107,7 +104,7 @@ void validate_xover(const double* freqs, int nfreq, int order, double fs) {
 
 // validateMultibandParams multiband.go:661-709
 void validate_multiband(const double* freqs, int nfreq, int order, double fs) {
-  if (!(fs > 0) || !finite(fs)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "multiband compressor: sample rate must be positive and finite");
+  if (!(fs > 0) || !is_finite(fs)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "multiband compressor: sample rate must be positive and finite");
   if (nfreq < 1 || !freqs) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "multiband compressor: at least one crossover frequency is required");
   if (nfreq + 1 > kXoverMaxStages + 1) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "multiband compressor: maximum 8 bands");
   if (order < 2 || order > kMaxOrder) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "multiband compressor: order must be in [2, 24]");
@@ -115,7 +112,7 @@ void validate_multiband(const double* freqs, int nfreq, int order, double fs) {
   const double nyquist = fs / 2;
   for (int i = 0; i < nfreq; ++i) {
     const double f = freqs[i];
-    if (!finite(f)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "multiband compressor: crossover frequency must be finite");
+    if (!is_finite(f)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "multiband compressor: crossover frequency must be finite");
     if (f < kMinCrossoverFrequency) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "multiband compressor: crossover frequency must be >= 20 Hz");
     if (f >= nyquist) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "multiband compressor: crossover frequency must be < Nyquist");
     if (i > 0 && f <= freqs[i - 1])
@@ -142,22 +139,6 @@ std::vector<double> design_table(const double* freqs, int nfreq, int order, doub
 void check_rc(int rc) {
   if (rc != AD_OK) AD_FAIL(rc, ad_last_error());
 }
-
-// One call of a handle on stream s: enter(s) now, leave(s) when the scope ends, by an exception too, so
-// that what was enqueued before a failure is still covered by the event the next call waits for.
-struct CallScope {
-  StreamOrder& calls;
-  hipStream_t s;
-  CallScope(StreamOrder& c, hipStream_t stream) : calls(c), s(stream) { calls.enter(s); }
-  CallScope(const CallScope&) = delete;
-  CallScope& operator=(const CallScope&) = delete;
-  ~CallScope() {
-    try {
-      calls.leave(s);
-    } catch (...) {  // the call's own error, if any, is the one to report
-    }
-  }
-};
 
 }  // namespace
 
@@ -254,7 +235,7 @@ void xover_reset(ad_xover* h) {
 }
 
 void xover_get_state(ad_xover* h, int channel, double* state, int64_t cap) {
-  if (channel < 0 || channel >= h->channels) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channel out of range");
+  check_channel(h, channel);
   const size_t per = h->per_channel();
   if (cap < (int64_t)per) AD_FAIL(AD_ERR_LENGTH_MISMATCH, "state buffer too small");
   if (!state) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null state buffer");
@@ -413,8 +394,7 @@ int ad_xover_get_state(ad_xover* h, int channel, double* state, int64_t cap) {
 
 int ad_xover_set_state(ad_xover* h, int channel, const double* state, int64_t n) {
   return guard([&] {
-    check_handle(h);
-    if (channel < 0 || channel >= h->channels) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channel out of range");
+    check_channel(h, channel);
     const size_t per = h->per_channel();
     if (n < (int64_t)per) AD_FAIL(AD_ERR_LENGTH_MISMATCH, "state too short");
     if (!state) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null state");

@@ -13,19 +13,15 @@
 #include <cstring>
 #include <memory>
 
-#include "ad_common.hpp"
+#include "fx_handle.hpp"
 #include "shaper_kernels.hpp"
-#include "stream_order.hpp"
 
 using namespace adsp;
 
 namespace {
 
-bool is_fin(double v) { return std::isfinite(v); }
-bool in_range(double v, double lo, double hi) { return v >= lo && v <= hi; }  // false for NaN
-
 void validate(const ad_distortion_config& c) {  // the setters :364-529, validate :590-605
-  if (!(c.sample_rate > 0) || !is_fin(c.sample_rate))
+  if (!(c.sample_rate > 0) || !is_finite(c.sample_rate))
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "distortion sample rate must be > 0 and finite");
   if (c.mode < 0 || c.mode >= SHAPE_MODES) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "distortion mode is invalid");
   if (c.approx < 0 || c.approx > 1) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "distortion approximation mode is invalid");
@@ -47,11 +43,11 @@ void validate(const ad_distortion_config& c) {  // the setters :364-529, validat
   if ((c.cheb_invert != 0 && c.cheb_invert != 1) || (c.cheb_dc_bypass != 0 && c.cheb_dc_bypass != 1))
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "chebyshev invert and DC bypass are 0 or 1");
   for (int k = 0; k < kChebMaxOrder; ++k)
-    if (!is_fin(c.cheb_weights[k])) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "chebyshev weights must be finite");
+    if (!is_finite(c.cheb_weights[k])) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "chebyshev weights must be finite");
 }
 
 void validate(const ad_bitcrusher_config& c) {  // NewBitCrusher :108-111, the setters :137-183
-  if (!(c.sample_rate > 0) || !is_fin(c.sample_rate))
+  if (!(c.sample_rate > 0) || !is_finite(c.sample_rate))
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bit crusher sample rate must be > 0 and finite");
   if (!in_range(c.bit_depth, 1, 32)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bit crusher bit depth must be in [1, 32]");
   if (c.downsample < 1 || c.downsample > 256)
@@ -86,29 +82,14 @@ ShapeParams shape_params(const ad_distortion_config& c) {
   return p;
 }
 
-// What the two handles share: the streams and the staging buffer of host calls.
-struct ShaperCore {
-  int device = 0, channels = 0;
-  hipStream_t stream = nullptr;  // host-buffer calls, resets, curve
-  StreamOrder order;             // calls may come on any stream
-  DevBuf<double> io;             // host-buffer calls
-  ~ShaperCore() {
-    order.release();
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      (void)lib_stream_destroy(stream);
-    }
-  }
-};
-
 }  // namespace
 
-struct ad_distortion : ShaperCore {
+struct ad_distortion : HandleCore {
   ad_distortion_config cfg{};
   DevBuf<double> dc;  // [channels][2] dcPrevIn, dcPrevOut
 };
 
-struct ad_bitcrusher : ShaperCore {
+struct ad_bitcrusher : HandleCore {
   ad_bitcrusher_config cfg{};
   double q = 0;          // quantLevels, updateQuantLevels :222-224
   int counter = 0;       // holdCounter
@@ -119,7 +100,7 @@ struct ad_bitcrusher : ShaperCore {
 namespace {
 
 void distortion_run(ad_distortion* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
-  f->order.enter(s);
+  CallScope call(f->order, s);
   const ShapeParams p = shape_params(f->cfg);
   if (f->cfg.mode == SHAPE_CHEBYSHEV && f->cfg.cheb_dc_bypass) {  // :545-547
     ShapeDcArgs a{};
@@ -140,14 +121,13 @@ void distortion_run(ad_distortion* f, double* d_buf, int64_t stride, int64_t n, 
     launch_shape(a, s);
   }
   AD_HIP(hipGetLastError());
-  f->order.leave(s);
 }
 
 // the first update sample of a call that starts with the counter at c0
 int64_t first_update(int downsample, int c0) { return std::max(downsample - 1 - c0, 0); }
 
 void bitcrusher_run(ad_bitcrusher* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
-  f->order.enter(s);
+  CallScope call(f->order, s);
   const int ds = f->cfg.downsample;
   const int64_t t0 = first_update(ds, f->counter);
   CrushArgs a{};
@@ -170,73 +150,6 @@ void bitcrusher_run(ad_bitcrusher* f, double* d_buf, int64_t stride, int64_t n, 
   } else {
     f->counter += (int)n;
   }
-  f->order.leave(s);
-}
-
-template <class H, class Cfg>
-int create(const Cfg* cfg, int channels, int device, H** out, void (*init)(H*)) {
-  if (out) *out = nullptr;
-  H* raw = nullptr;
-  const int rc = guard([&] {
-    if (!out) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null output handle");
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null config");
-    if (channels <= 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channels must be positive");
-    validate(*cfg);
-    const int dev = pick_device(device);
-    DeviceScope ds(dev);
-    std::unique_ptr<H> f(new H());
-    f->device = dev;
-    f->channels = channels;
-    f->cfg = *cfg;
-    AD_HIP(lib_stream_create(&f->stream));
-    init(f.get());
-    AD_HIP(hipStreamSynchronize(f->stream));
-    raw = f.release();
-  });
-  if (rc == AD_OK && out) *out = raw;
-  return rc;
-}
-
-template <class H, class Run>
-int process_host(H* f, double* buf, int64_t n, Run run) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || (n > 0 && !buf)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    const size_t count = (size_t)f->channels * n;
-    f->io.reserve(count);
-    AD_HIP(hipMemcpyAsync(f->io.p, buf, count * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    run(f, f->io.p, n, n, f->stream);
-    AD_HIP(hipMemcpyAsync(buf, f->io.p, count * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    AD_HIP(hipStreamSynchronize(f->stream));
-  });
-}
-
-template <class H, class Run>
-int process_dev(H* f, double* d_buf, int64_t stride, int64_t n, void* stream, Run run) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || (n > 0 && (!d_buf || stride < n))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer geometry");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    run(f, d_buf, stride, n, reinterpret_cast<hipStream_t>(stream));
-  });
-}
-
-template <class H>
-void destroy(H* f) {
-  if (!f) return;
-  (void)guard([&] {
-    DeviceScope ds(f->device);
-    delete f;
-  });
-}
-
-// a whole number in [lo, hi], as the reference's int and bool setters take
-int whole(double v, int lo, int hi, const char* what) {
-  if (!in_range(v, lo, hi) || v != std::floor(v)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, what);
-  return (int)v;
 }
 
 }  // namespace
@@ -258,23 +171,17 @@ void ad_distortion_default_config(ad_distortion_config* cfg, double sample_rate)
   cfg->cheb_order = 3;
 }
 
-int ad_distortion_validate(const ad_distortion_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null distortion config");
-    validate(*cfg);
-  });
-}
+int ad_distortion_validate(const ad_distortion_config* cfg) { return validate_config(cfg, validate); }
 
 int ad_distortion_create(const ad_distortion_config* cfg, int channels, int device, ad_distortion** out) {
-  return create<ad_distortion>(cfg, channels, device, out, +[](ad_distortion* f) {
+  return create_handle(cfg, channels, device, out, validate, [](ad_distortion* f, const ad_distortion_config&) {
     f->dc.alloc((size_t)f->channels * 2);
-    AD_HIP(hipMemsetAsync(f->dc.p, 0, f->dc.n * sizeof(double), f->stream));
+    zero(f->dc, f->stream);
   });
 }
 
 int ad_distortion_set_param(ad_distortion* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null distortion handle");
+  return with_handle(f, [&] {
     ad_distortion_config c = f->cfg;
     switch (which) {
       case AD_DISTORTION_SAMPLE_RATE: c.sample_rate = value; break;    // SetSampleRate :365-373
@@ -311,12 +218,11 @@ int ad_distortion_set_param(ad_distortion* f, int which, double value) {
 }
 
 int ad_distortion_set_weights(ad_distortion* f, const double* w, int n) {
-  return guard([&] {  // SetChebyshevWeights :514-529
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null distortion handle");
+  return with_handle(f, [&] {  // SetChebyshevWeights :514-529
     if (n < 0 || n > kChebMaxOrder || (n > 0 && !w))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "chebyshev weights length must be <= 16");
     for (int k = 0; k < n; ++k)
-      if (!is_fin(w[k])) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "chebyshev weights must be finite");
+      if (!is_finite(w[k])) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "chebyshev weights must be finite");
     std::memset(f->cfg.cheb_weights, 0, sizeof(f->cfg.cheb_weights));
     if (n > 0) std::memcpy(f->cfg.cheb_weights, w, (size_t)n * sizeof(double));
   });
@@ -331,8 +237,7 @@ int ad_distortion_get_config(const ad_distortion* f, ad_distortion_config* cfg) 
 
 int ad_distortion_derived(const ad_distortion* f, double* atan_scale, double* scale6, double* scale2,
                           double* one_minus_mix, int* weights_active) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null distortion handle");
+  return with_handle(f, [&] {
     const ShapeParams p = shape_params(f->cfg);
     if (atan_scale) *atan_scale = p.atan_scale4;
     if (scale6) *scale6 = p.scale6;
@@ -344,8 +249,7 @@ int ad_distortion_derived(const ad_distortion* f, double* atan_scale, double* sc
 
 int ad_distortion_kernel_info(const ad_distortion* f, int* samples_per_workgroup, int* dc_channels_per_workgroup,
                               int* dc_tile, int* dc_lds_bytes) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null distortion handle");
+  return with_handle(f, [&] {
     if (samples_per_workgroup) *samples_per_workgroup = 2 * kShapeThreads * kShapeSteps;
     if (dc_channels_per_workgroup) *dc_channels_per_workgroup = 64;
     if (dc_tile) *dc_tile = kDcTile;
@@ -354,11 +258,9 @@ int ad_distortion_kernel_info(const ad_distortion* f, int* samples_per_workgroup
 }
 
 int ad_distortion_curve(ad_distortion* f, const double* x, int64_t n, double* wet) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null distortion handle");
+  return with_handle(f, [&] {
     if (n < 0 || (n > 0 && (!x || !wet))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad curve buffers");
     if (n == 0) return;
-    DeviceScope ds(f->device);
     DevBuf<double> dx, dw;  // a plot, not a hot path: buffers of its own, so no call's staging is touched
     dx.alloc((size_t)n);
     dw.alloc((size_t)n);
@@ -373,21 +275,19 @@ int ad_distortion_curve(ad_distortion* f, const double* x, int64_t n, double* we
 int ad_distortion_process(ad_distortion* f, double* buf, int64_t n) { return process_host(f, buf, n, distortion_run); }
 
 int ad_distortion_process_device(ad_distortion* f, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return process_dev(f, d_buf, stride, n, stream, distortion_run);
+  return process_device(f, d_buf, stride, n, stream, distortion_run);
 }
 
 int ad_distortion_reset(ad_distortion* f) {
   // Reset :532-535: dcPrevIn, dcPrevOut; ordered after the last call
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null distortion handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
-    AD_HIP(hipMemsetAsync(f->dc.p, 0, f->dc.n * sizeof(double), f->stream));
+    zero(f->dc, f->stream);
     AD_HIP(hipStreamSynchronize(f->stream));
   });
 }
 
-void ad_distortion_destroy(ad_distortion* f) { destroy(f); }
+void ad_distortion_destroy(ad_distortion* f) { destroy_handle(f); }
 
 // ---- ad_bitcrusher ----------------------------------------------------------
 void ad_bitcrusher_default_config(ad_bitcrusher_config* cfg, double sample_rate) {
@@ -399,24 +299,18 @@ void ad_bitcrusher_default_config(ad_bitcrusher_config* cfg, double sample_rate)
   cfg->downsample = 1;
 }
 
-int ad_bitcrusher_validate(const ad_bitcrusher_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null bit crusher config");
-    validate(*cfg);
-  });
-}
+int ad_bitcrusher_validate(const ad_bitcrusher_config* cfg) { return validate_config(cfg, validate); }
 
 int ad_bitcrusher_create(const ad_bitcrusher_config* cfg, int channels, int device, ad_bitcrusher** out) {
-  return create<ad_bitcrusher>(cfg, channels, device, out, +[](ad_bitcrusher* f) {
-    f->q = std::exp2(f->cfg.bit_depth - 1);
+  return create_handle(cfg, channels, device, out, validate, [](ad_bitcrusher* f, const ad_bitcrusher_config& c) {
+    f->q = std::exp2(c.bit_depth - 1);
     f->hold.alloc((size_t)f->channels * 2);
-    AD_HIP(hipMemsetAsync(f->hold.p, 0, f->hold.n * sizeof(double), f->stream));
+    zero(f->hold, f->stream);
   });
 }
 
 int ad_bitcrusher_set_param(ad_bitcrusher* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null bit crusher handle");
+  return with_handle(f, [&] {
     ad_bitcrusher_config c = f->cfg;
     switch (which) {
       case AD_BITCRUSHER_SAMPLE_RATE: c.sample_rate = value; break;  // SetSampleRate :138-146
@@ -442,8 +336,7 @@ int ad_bitcrusher_get_config(const ad_bitcrusher* f, ad_bitcrusher_config* cfg) 
 
 int ad_bitcrusher_derived(ad_bitcrusher* f, int channel, double* quant_levels, int* counter, double* hold_value) {
   return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null bit crusher handle");
-    if (channel < 0 || channel >= f->channels) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bit crusher channel out of range");
+    check_channel(f, channel);
     if (quant_levels) *quant_levels = f->q;
     if (counter) *counter = f->counter;
     if (hold_value) {
@@ -456,8 +349,7 @@ int ad_bitcrusher_derived(ad_bitcrusher* f, int channel, double* quant_levels, i
 }
 
 int ad_bitcrusher_kernel_info(const ad_bitcrusher* f, int* samples_per_workgroup, int* span, int* lds_bytes) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null bit crusher handle");
+  return with_handle(f, [&] {
     const bool pointwise = f->cfg.downsample == 1;
     if (samples_per_workgroup)
       *samples_per_workgroup = pointwise ? 2 * kShapeThreads * kShapeSteps : (int)crush_span(f->cfg.downsample);
@@ -469,21 +361,19 @@ int ad_bitcrusher_kernel_info(const ad_bitcrusher* f, int* samples_per_workgroup
 int ad_bitcrusher_process(ad_bitcrusher* f, double* buf, int64_t n) { return process_host(f, buf, n, bitcrusher_run); }
 
 int ad_bitcrusher_process_device(ad_bitcrusher* f, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return process_dev(f, d_buf, stride, n, stream, bitcrusher_run);
+  return process_device(f, d_buf, stride, n, stream, bitcrusher_run);
 }
 
 int ad_bitcrusher_reset(ad_bitcrusher* f) {
   // Reset :186-189: holdCounter = 0, holdValue = 0; ordered after the last call
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null bit crusher handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
-    AD_HIP(hipMemsetAsync(f->hold.p, 0, f->hold.n * sizeof(double), f->stream));
+    zero(f->hold, f->stream);
     AD_HIP(hipStreamSynchronize(f->stream));
     f->counter = 0;
   });
 }
 
-void ad_bitcrusher_destroy(ad_bitcrusher* f) { destroy(f); }
+void ad_bitcrusher_destroy(ad_bitcrusher* f) { destroy_handle(f); }
 
 }  // extern "C"

@@ -8,15 +8,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <memory>
 #include <numeric>
 #include <vector>
 
-#include "ad_common.hpp"
+#include "fx_handle.hpp"
 #include "stft_kernels.hpp"
-#include "stream_order.hpp"
 
 using namespace adsp;
 
@@ -27,8 +27,6 @@ constexpr double kBinShiftThreshold = 0.15;        // pitch_shift_spectral.go:24
 constexpr double kIdentityEps = 1e-9;              // pitch_shifter.go:29
 constexpr double kMinRatio = 0.25, kMaxRatio = 4.0;  // pitch_shifter.go:19-20
 constexpr int64_t kMaxSamples = (int64_t)1 << 31;
-
-bool positive(double v) { return v > 0 && std::isfinite(v); }
 
 void check_frame(int size, const char* who) {
   if (size < kStftMinFrame || !is_pow2(size))
@@ -67,21 +65,13 @@ void validate(const ad_pitchspec_config& c) {  // validate pitch_shift_spectral.
   if (c.resample_taps && c.n_resample_taps <= 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "resampling prototype without taps");
 }
 
-int whole(double value, const char* msg) {
-  if (!(value >= -2147483648.0 && value <= 2147483647.0) || value != std::floor(value)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, msg);
-  return (int)value;
-}
 
-// What the two handles share: the tables, the scratch rows and the streams.
-struct StftCore {
-  int device = 0, channels = 0;
+// What the two handles share: the tables and the scratch rows.
+struct StftCore : HandleCore {
   int frame = 0;
   std::vector<double> h_win;
   DevBuf<double> win, omega;     // [N], [N/2 + 1]
   DevBuf<double> rows;           // [group][frames][N + 2]
-  hipStream_t stream = nullptr;  // host-buffer calls, resets, state access
-  StreamOrder order;             // calls may come on any stream
-  DevBuf<double> io;             // host-buffer calls
   // ad_*_profile: events between the passes of the calls made while it is on
   bool profiling = false;
   std::vector<std::pair<int, hipEvent_t>> marks;  // (the pass that ends here, or -1: a group starts)
@@ -108,14 +98,7 @@ struct StftCore {
     for (auto& m : marks) (void)hipEventDestroy(m.second);
     marks.clear();
   }
-  ~StftCore() {
-    drop_marks();
-    order.release();
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      (void)lib_stream_destroy(stream);
-    }
-  }
+  ~StftCore() { drop_marks(); }
   int bins() const { return frame / 2 + 1; }
   // rebuildState's tables (spectral_freeze.go:388-400): the caller's window, omega[k] = 2*pi*k/N
   void set_tables(int n, const double* window) {
@@ -193,8 +176,6 @@ struct ad_pitchspec : StftCore {
 
 namespace {
 
-void zero(DevBuf<double>& b, hipStream_t s) { AD_HIP(hipMemsetAsync(b.p, 0, b.n * sizeof(double), s)); }
-
 // rebuildState :371-410: new tables, cleared capture
 void freeze_rebuild(ad_specfreeze* f, int n, const double* window) {
   DeviceScope ds(f->device);
@@ -209,7 +190,7 @@ void freeze_rebuild(ad_specfreeze* f, int n, const double* window) {
 }
 
 void freeze_run(ad_specfreeze* f, double* d_buf, int64_t stride, int64_t n, hipStream_t s) {
-  f->order.enter(s);
+  CallScope call(f->order, s);
   const int hop = f->cfg.hop_size, N = f->frame, B = f->bins();
   const int64_t frames = 1 + (n - 1) / hop;  // ProcessWithError :220-221
   const int64_t pitch = stft_pitch(N);
@@ -257,7 +238,6 @@ void freeze_run(ad_specfreeze* f, double* d_buf, int64_t stride, int64_t n, hipS
   }
   AD_HIP(hipGetLastError());
   if (capture) f->has_frozen = true;
-  f->order.leave(s);
 }
 
 int pitch_path(const ad_pitchspec* p) {
@@ -299,7 +279,7 @@ void pitch_run(ad_pitchspec* p, double* d_buf, int64_t stride, int64_t n, hipStr
   const bool resample = shop != hop;
   if (resample && p->taps.empty())
     AD_FAIL(AD_ERR_INVALID_ARGUMENT, "spectral pitch shifter: the time stretch needs a resampling prototype for its hops");
-  p->order.enter(s);
+  CallScope call(p->order, s);
   const int64_t frames = 1 + (n - 1) / hop;  // :291, :396
   const int64_t pitch = stft_pitch(N);
   const int G = p->group(frames);
@@ -360,82 +340,17 @@ void pitch_run(ad_pitchspec* p, double* d_buf, int64_t stride, int64_t n, hipStr
     p->mark(AD_STFT_PASS_RESAMPLE, s);
   }
   AD_HIP(hipGetLastError());
-  p->order.leave(s);
-}
-
-template <class H, class Cfg>
-int create(const Cfg* cfg, int channels, int device, H** out, void (*init)(H*, const Cfg&)) {
-  if (out) *out = nullptr;
-  H* raw = nullptr;
-  const int rc = guard([&] {
-    if (!out) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null output handle");
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null config");
-    if (channels <= 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channels must be positive");
-    validate(*cfg);
-    const int dev = pick_device(device);
-    DeviceScope ds(dev);
-    std::unique_ptr<H> f(new H());
-    f->device = dev;
-    f->channels = channels;
-    f->cfg = *cfg;
-    AD_HIP(lib_stream_create(&f->stream));
-    init(f.get(), *cfg);
-    f->cfg.window = nullptr;
-    AD_HIP(hipStreamSynchronize(f->stream));
-    raw = f.release();
-  });
-  if (rc == AD_OK && out) *out = raw;
-  return rc;
-}
-
-template <class H, class Run>
-int process_host(H* f, double* buf, int64_t n, Run run) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || n >= kMaxSamples || (n > 0 && !buf)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    const size_t count = (size_t)f->channels * n;
-    f->order.wait_host();
-    f->io.reserve(count);
-    AD_HIP(hipMemcpyAsync(f->io.p, buf, count * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    run(f, f->io.p, n, n, f->stream);
-    AD_HIP(hipMemcpyAsync(buf, f->io.p, count * sizeof(double), hipMemcpyDeviceToHost, f->stream));
-    AD_HIP(hipStreamSynchronize(f->stream));
-  });
-}
-
-template <class H, class Run>
-int process_dev(H* f, double* d_buf, int64_t stride, int64_t n, void* stream, Run run) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null handle");
-    if (n < 0 || n >= kMaxSamples || (n > 0 && (!d_buf || stride < n))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer geometry");
-    if (n == 0) return;
-    DeviceScope ds(f->device);
-    run(f, d_buf, stride, n, reinterpret_cast<hipStream_t>(stream));
-  });
 }
 
 template <class H>
 int profile(H* f, int enable, double* ms) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
     if (ms)
       f->read_marks(ms);
     else
       f->drop_marks();
     f->profiling = enable != 0;
-  });
-}
-
-template <class H>
-void destroy(H* f) {
-  if (!f) return;
-  (void)guard([&] {
-    DeviceScope ds(f->device);
-    delete f;
   });
 }
 
@@ -456,29 +371,31 @@ void ad_specfreeze_default_config(ad_specfreeze_config* cfg, double sample_rate)
   cfg->frozen = 0;
 }
 
-int ad_specfreeze_validate(const ad_specfreeze_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral freeze config");
-    validate(*cfg);
+int ad_specfreeze_validate(const ad_specfreeze_config* cfg) { return validate_config(cfg, validate); }
+
+int ad_specfreeze_create(const ad_specfreeze_config* cfg, int channels, int device, ad_specfreeze** out) {
+  return create_handle(cfg, channels, device, out, validate, [](ad_specfreeze* f, const ad_specfreeze_config& c) {
+    freeze_rebuild(f, c.frame_size, c.window);
+    f->cfg.window = nullptr;
   });
 }
 
-int ad_specfreeze_create(const ad_specfreeze_config* cfg, int channels, int device, ad_specfreeze** out) {
-  return create<ad_specfreeze, ad_specfreeze_config>(
-      cfg, channels, device, out, +[](ad_specfreeze* f, const ad_specfreeze_config& c) { freeze_rebuild(f, c.frame_size, c.window); });
-}
-
 int ad_specfreeze_set_param(ad_specfreeze* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral freeze handle");
+  return with_handle(f, [&] {
     ad_specfreeze_config c = f->cfg;
     c.window = f->h_win.data();
     switch (which) {
       case AD_SPECFREEZE_SAMPLE_RATE: c.sample_rate = value; break;
-      case AD_SPECFREEZE_HOP: c.hop_size = whole(value, "spectral freeze hop size must be a whole number"); break;
+      case AD_SPECFREEZE_HOP:
+        c.hop_size = whole(value, INT_MIN, INT_MAX, "spectral freeze hop size must be a whole number");
+        break;
       case AD_SPECFREEZE_MIX: c.mix = value; break;
-      case AD_SPECFREEZE_PHASE_MODE: c.phase_mode = whole(value, "spectral freeze phase mode invalid"); break;
-      case AD_SPECFREEZE_FROZEN: c.frozen = whole(value, "spectral freeze frozen must be 0 or 1"); break;
+      case AD_SPECFREEZE_PHASE_MODE:
+        c.phase_mode = whole(value, INT_MIN, INT_MAX, "spectral freeze phase mode invalid");
+        break;
+      case AD_SPECFREEZE_FROZEN:
+        c.frozen = whole(value, INT_MIN, INT_MAX, "spectral freeze frozen must be 0 or 1");
+        break;
       default: AD_FAIL(AD_ERR_INVALID_ARGUMENT, "unknown spectral freeze parameter");
     }
     validate(c);  // every other field is valid already: the setter's own check
@@ -489,8 +406,7 @@ int ad_specfreeze_set_param(ad_specfreeze* f, int which, double value) {
 }
 
 int ad_specfreeze_set_frame(ad_specfreeze* f, int frame_size, const double* window) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral freeze handle");
+  return with_handle(f, [&] {
     check_frame(frame_size, "spectral freeze");
     check_window(window, frame_size, "spectral freeze");
     f->cfg.frame_size = frame_size;  // SetFrameSize :115-127
@@ -500,8 +416,7 @@ int ad_specfreeze_set_frame(ad_specfreeze* f, int frame_size, const double* wind
 }
 
 int ad_specfreeze_set_window(ad_specfreeze* f, int window_type, const double* window) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral freeze handle");
+  return with_handle(f, [&] {
     check_window(window, f->frame, "spectral freeze");
     f->cfg.window_type = window_type;  // SetWindowType :152-155
     const std::vector<double> w(window, window + f->frame);  // window may be h_win itself
@@ -517,9 +432,7 @@ int ad_specfreeze_get_config(const ad_specfreeze* f, ad_specfreeze_config* cfg) 
 }
 
 int ad_specfreeze_state(ad_specfreeze* f, double* held_magnitude, double* phase_acc, int* has_frozen) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral freeze handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
     const size_t bytes = (size_t)f->channels * f->bins() * sizeof(double);
     if (held_magnitude) AD_HIP(hipMemcpy(held_magnitude, f->held.p, bytes, hipMemcpyDeviceToHost));
@@ -529,11 +442,9 @@ int ad_specfreeze_state(ad_specfreeze* f, double* held_magnitude, double* phase_
 }
 
 int ad_specfreeze_norm(ad_specfreeze* f, double* norm, int64_t n) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral freeze handle");
+  return with_handle(f, [&] {
     if (n < 0 || n >= kMaxSamples || (n > 0 && !norm)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer");
     if (n == 0) return;
-    DeviceScope ds(f->device);
     f->order.wait_host();
     f->io.reserve((size_t)n);
     StftOlaArgs o = f->ola_args(f->cfg.hop_size, 1 + (n - 1) / f->cfg.hop_size, f->io.p, n, n, 1);
@@ -545,17 +456,15 @@ int ad_specfreeze_norm(ad_specfreeze* f, double* norm, int64_t n) {
   });
 }
 
-int ad_specfreeze_process(ad_specfreeze* f, double* buf, int64_t n) { return process_host(f, buf, n, freeze_run); }
+int ad_specfreeze_process(ad_specfreeze* f, double* buf, int64_t n) { return process_host(f, buf, n, freeze_run, kMaxSamples); }
 
 int ad_specfreeze_process_device(ad_specfreeze* f, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return process_dev(f, d_buf, stride, n, stream, freeze_run);
+  return process_device(f, d_buf, stride, n, stream, freeze_run, kMaxSamples);
 }
 
 int ad_specfreeze_reset(ad_specfreeze* f) {
   // Reset :184-189: the captured frame and the phase accumulators; ordered after the last call
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral freeze handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     f->order.wait_host();
     zero(f->acc, f->stream);
     AD_HIP(hipStreamSynchronize(f->stream));
@@ -565,7 +474,7 @@ int ad_specfreeze_reset(ad_specfreeze* f) {
 
 int ad_specfreeze_profile(ad_specfreeze* f, int enable, double* ms) { return profile(f, enable, ms); }
 
-void ad_specfreeze_destroy(ad_specfreeze* f) { destroy(f); }
+void ad_specfreeze_destroy(ad_specfreeze* f) { destroy_handle(f); }
 
 // ---- ad_pitchspec -----------------------------------------------------------
 void ad_pitchspec_default_config(ad_pitchspec_config* cfg, double sample_rate) {
@@ -579,34 +488,31 @@ void ad_pitchspec_default_config(ad_pitchspec_config* cfg, double sample_rate) {
   cfg->resample_quality = 1;  // resample.QualityBalanced
 }
 
-int ad_pitchspec_validate(const ad_pitchspec_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral pitch shifter config");
-    validate(*cfg);
+int ad_pitchspec_validate(const ad_pitchspec_config* cfg) { return validate_config(cfg, validate); }
+
+int ad_pitchspec_create(const ad_pitchspec_config* cfg, int channels, int device, ad_pitchspec** out) {
+  return create_handle(cfg, channels, device, out, validate, [](ad_pitchspec* p, const ad_pitchspec_config& c) {
+    pitch_rebuild(p, c.frame_size, c.window);
+    pitch_update_hop(p);
+    if (c.resample_taps) pitch_install_taps(p, c.resample_taps, c.n_resample_taps);
+    p->cfg.window = p->cfg.resample_taps = nullptr;
+    p->cfg.n_resample_taps = 0;
   });
 }
 
-int ad_pitchspec_create(const ad_pitchspec_config* cfg, int channels, int device, ad_pitchspec** out) {
-  return create<ad_pitchspec, ad_pitchspec_config>(
-      cfg, channels, device, out, +[](ad_pitchspec* p, const ad_pitchspec_config& c) {
-        pitch_rebuild(p, c.frame_size, c.window);
-        pitch_update_hop(p);
-        if (c.resample_taps) pitch_install_taps(p, c.resample_taps, c.n_resample_taps);
-        p->cfg.resample_taps = nullptr;
-        p->cfg.n_resample_taps = 0;
-      });
-}
-
 int ad_pitchspec_set_param(ad_pitchspec* p, int which, double value) {
-  return guard([&] {
-    if (!p) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral pitch shifter handle");
+  return with_handle(p, [&] {
     ad_pitchspec_config c = p->cfg;
     c.window = p->h_win.data();
     switch (which) {
       case AD_PITCHSPEC_SAMPLE_RATE: c.sample_rate = value; break;
       case AD_PITCHSPEC_RATIO: c.pitch_ratio = value; break;
-      case AD_PITCHSPEC_HOP: c.analysis_hop = whole(value, "spectral analysis hop must be a whole number"); break;
-      case AD_PITCHSPEC_RESAMPLE_QUALITY: c.resample_quality = whole(value, "resample quality must be a whole number"); break;
+      case AD_PITCHSPEC_HOP:
+        c.analysis_hop = whole(value, INT_MIN, INT_MAX, "spectral analysis hop must be a whole number");
+        break;
+      case AD_PITCHSPEC_RESAMPLE_QUALITY:
+        c.resample_quality = whole(value, INT_MIN, INT_MAX, "resample quality must be a whole number");
+        break;
       default: AD_FAIL(AD_ERR_INVALID_ARGUMENT, "unknown spectral pitch shifter parameter");
     }
     validate(c);
@@ -623,8 +529,7 @@ int ad_pitchspec_set_param(ad_pitchspec* p, int which, double value) {
 }
 
 int ad_pitchspec_set_frame(ad_pitchspec* p, int frame_size, const double* window) {
-  return guard([&] {
-    if (!p) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral pitch shifter handle");
+  return with_handle(p, [&] {
     check_frame(frame_size, "spectral");
     check_window(window, frame_size, "spectral pitch shifter");
     p->order.wait_host();
@@ -640,8 +545,7 @@ int ad_pitchspec_set_frame(ad_pitchspec* p, int frame_size, const double* window
 }
 
 int ad_pitchspec_set_window(ad_pitchspec* p, int window_type, const double* window) {
-  return guard([&] {
-    if (!p) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral pitch shifter handle");
+  return with_handle(p, [&] {
     check_window(window, p->frame, "spectral pitch shifter");
     p->cfg.window_type = window_type;  // SetWindowType :211-214
     const std::vector<double> w(window, window + p->frame);
@@ -650,8 +554,7 @@ int ad_pitchspec_set_window(ad_pitchspec* p, int window_type, const double* wind
 }
 
 int ad_pitchspec_set_resample_taps(ad_pitchspec* p, const double* taps, int64_t n_taps) {
-  return guard([&] {
-    if (!p) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral pitch shifter handle");
+  return with_handle(p, [&] {
     pitch_install_taps(p, taps, n_taps);
   });
 }
@@ -687,21 +590,20 @@ int ad_pitchspec_path(const ad_pitchspec* p, int* path) {
   });
 }
 
-int ad_pitchspec_process(ad_pitchspec* p, double* buf, int64_t n) { return process_host(p, buf, n, pitch_run); }
+int ad_pitchspec_process(ad_pitchspec* p, double* buf, int64_t n) { return process_host(p, buf, n, pitch_run, kMaxSamples); }
 
 int ad_pitchspec_process_device(ad_pitchspec* p, double* d_buf, int64_t stride, int64_t n, void* stream) {
-  return process_dev(p, d_buf, stride, n, stream, pitch_run);
+  return process_device(p, d_buf, stride, n, stream, pitch_run, kMaxSamples);
 }
 
 int ad_pitchspec_reset(ad_pitchspec* p) {
   // Reset :222-227 clears prevPhase and sumPhase, which every call clears itself: nothing is kept between calls
-  return guard([&] {
-    if (!p) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null spectral pitch shifter handle");
+  return with_handle(p, [&] {
   });
 }
 
 int ad_pitchspec_profile(ad_pitchspec* p, int enable, double* ms) { return profile(p, enable, ms); }
 
-void ad_pitchspec_destroy(ad_pitchspec* p) { destroy(p); }
+void ad_pitchspec_destroy(ad_pitchspec* p) { destroy_handle(p); }
 
 }  // extern "C"

@@ -14,8 +14,7 @@
 #include <memory>
 #include <vector>
 
-#include "ad_common.hpp"
-#include "stream_order.hpp"
+#include "fx_handle.hpp"
 #include "vocoder_kernels.hpp"
 
 using namespace adsp;
@@ -30,10 +29,6 @@ constexpr double kThirdOctaveFreqs[32] = {16,  20,  25,  31,   40,   50,   63,  
 constexpr double kBarkFreqs[24] = {100,  200,  300,  400,  510,  630,  770,  920,  1080, 1270, 1480,  1720,
                                    2000, 2320, 2700, 3150, 3700, 4400, 5300, 6400, 7700, 9500, 12000, 15500};  // :33-36
 constexpr double kThirdOctaveQ = 4.3184727050832485;  // :39
-
-bool finite(double v) { return std::isfinite(v); }
-bool in_range(double v, double lo, double hi) { return v >= lo && v <= hi; }  // false for NaN
-bool flag(int v) { return v == 0 || v == 1; }
 
 struct Layout {
   const double* freqs;
@@ -51,7 +46,7 @@ int usable_bands(const ad_vocoder_config& c) {  // :309-318, :351-359
 }
 
 void validate(const ad_vocoder_config& c) {
-  if (!(c.sample_rate > 0) || !finite(c.sample_rate)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "vocoder: sample rate must be > 0");
+  if (!(c.sample_rate > 0) || !is_finite(c.sample_rate)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "vocoder: sample rate must be > 0");
   if (!flag(c.layout)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "vocoder: invalid band layout");
   if (!in_range(c.synth_q, 0.1, 20)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "vocoder: synthesis Q must be in [0.1, 20]");
   if (!in_range(c.attack_ms, 0.01, 100)) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "vocoder: attack must be in [0.01, 100] ms");
@@ -162,24 +157,13 @@ ad_vocoder_tables derive(const ad_vocoder_config& c) {
 
 }  // namespace
 
-struct ad_vocoder {
-  int device = 0, channels = 0;
+struct ad_vocoder : HandleCore {
   ad_vocoder_config cfg{};
   ad_vocoder_tables t{};
   int counter = 0;               // downsampleCount
   DevBuf<double> state;          // [channels][VOC_STATE_ROWS][kVocBands]
   DevBuf<double> tab;            // [VOC_TAB_ROWS][kVocBands]
   DevBuf<int> itab;              // [VOC_INT_ROWS][kVocBands]
-  hipStream_t stream = nullptr;  // host-buffer calls, resets, table uploads
-  StreamOrder order;             // calls may come on any stream
-  DevBuf<double> io;             // host-buffer calls
-  ~ad_vocoder() {
-    order.release();
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      (void)lib_stream_destroy(stream);
-    }
-  }
 };
 
 namespace {
@@ -226,7 +210,7 @@ bool overlap(const double* a, int64_t a_stride, const double* b, int64_t b_strid
 
 void run(ad_vocoder* f, const double* mod, int64_t ms, const double* car, int64_t cs, double* out, int64_t os, int64_t n,
          hipStream_t s) {
-  f->order.enter(s);
+  CallScope call(f->order, s);
   VocArgs a{};
   a.mod = mod, a.car = car, a.out = out;
   a.mod_stride = ms, a.car_stride = cs, a.out_stride = os, a.n = n;
@@ -243,7 +227,6 @@ void run(ad_vocoder* f, const double* mod, int64_t ms, const double* car, int64_
   launch_vocoder(a, ds, s);
   AD_HIP(hipGetLastError());
   if (ds) f->counter = (int)((f->counter + n) & (int64_t)(f->t.downsample_max - 1));  // :608-611, downsampleMax = 2^k
-  f->order.leave(s);
 }
 
 }  // namespace
@@ -262,12 +245,7 @@ void ad_vocoder_default_config(ad_vocoder_config* cfg, double sample_rate) {
   cfg->vocoder_level = 1.0;
 }
 
-int ad_vocoder_validate(const ad_vocoder_config* cfg) {
-  return guard([&] {
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null vocoder config");
-    validate(*cfg);
-  });
-}
+int ad_vocoder_validate(const ad_vocoder_config* cfg) { return validate_config(cfg, validate); }
 
 int ad_vocoder_derived(const ad_vocoder_config* cfg, ad_vocoder_tables* out) {
   return guard([&] {
@@ -278,36 +256,19 @@ int ad_vocoder_derived(const ad_vocoder_config* cfg, ad_vocoder_tables* out) {
 }
 
 int ad_vocoder_create(const ad_vocoder_config* cfg, int channels, int device, ad_vocoder** out) {
-  if (out) *out = nullptr;
-  ad_vocoder* raw = nullptr;
-  const int rc = guard([&] {
-    if (!out) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null output handle");
-    if (!cfg) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null config");
-    if (channels <= 0) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channels must be positive");
-    validate(*cfg);
-    const int dev = pick_device(device);
-    DeviceScope ds(dev);
-    std::unique_ptr<ad_vocoder> f(new ad_vocoder());
-    f->device = dev;
-    f->channels = channels;
-    f->cfg = *cfg;
-    f->t = derive(*cfg);
-    AD_HIP(lib_stream_create(&f->stream));
-    f->state.alloc((size_t)channels * VOC_STATE_ROWS * kVocBands);
+  return create_handle(cfg, channels, device, out, validate, [](ad_vocoder* f, const ad_vocoder_config& c) {
+    f->t = derive(c);
+    f->state.alloc((size_t)f->channels * VOC_STATE_ROWS * kVocBands);
     f->tab.alloc((size_t)VOC_TAB_ROWS * kVocBands);
     f->itab.alloc((size_t)VOC_INT_ROWS * kVocBands);
-    AD_HIP(hipMemsetAsync(f->state.p, 0, f->state.n * sizeof(double), f->stream));
+    zero(f->state, f->stream);
     AD_HIP(hipStreamSynchronize(f->stream));
-    upload(f.get());
-    raw = f.release();
+    upload(f);
   });
-  if (rc == AD_OK && out) *out = raw;
-  return rc;
 }
 
 int ad_vocoder_set_param(ad_vocoder* f, int which, double value) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null vocoder handle");
+  return with_handle(f, [&] {
     ad_vocoder_config c = f->cfg;
     switch (which) {
       case AD_VOCODER_SAMPLE_RATE: c.sample_rate = value; break;      // SetSampleRate :673-683
@@ -327,7 +288,6 @@ int ad_vocoder_set_param(ad_vocoder* f, int which, double value) {
       f->cfg = c;  // the next call's arguments
       return;
     }
-    DeviceScope ds(f->device);
     const ad_vocoder_tables t = derive(c);
     if (which == AD_VOCODER_SAMPLE_RATE) {
       // v.envelopes = nil and buildFilterBanks: new sections everywhere.  The decimation sections and the
@@ -373,8 +333,7 @@ int ad_vocoder_downsample_factors(const ad_vocoder* f, int* factors, int cap, in
 }
 
 int ad_vocoder_kernel_info(const ad_vocoder* f, int* lanes_per_channel, int* tile, int* lds_bytes) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null vocoder handle");
+  return with_handle(f, [&] {
     if (lanes_per_channel) *lanes_per_channel = 64;
     if (tile) *tile = kVocTile;
     if (lds_bytes) *lds_bytes = kVocLdsBytes;
@@ -383,8 +342,7 @@ int ad_vocoder_kernel_info(const ad_vocoder* f, int* lanes_per_channel, int* til
 
 int ad_vocoder_get_state(ad_vocoder* f, int channel, double* state, int* counter) {
   return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null vocoder handle");
-    if (channel < 0 || channel >= f->channels) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "channel out of range");
+    check_channel(f, channel);
     DeviceScope ds(f->device);
     f->order.wait_host();
     const size_t per = (size_t)VOC_STATE_ROWS * kVocBands;
@@ -394,11 +352,9 @@ int ad_vocoder_get_state(ad_vocoder* f, int channel, double* state, int* counter
 }
 
 int ad_vocoder_process(ad_vocoder* f, const double* modulator, const double* carrier, double* out, int64_t n) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null vocoder handle");
+  return with_handle(f, [&] {
     if (n < 0 || (n > 0 && (!modulator || !carrier || !out))) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer");
     if (n == 0) return;
-    DeviceScope ds(f->device);
     const size_t count = (size_t)f->channels * n;
     f->order.wait_host();
     f->io.reserve(2 * count);
@@ -414,8 +370,7 @@ int ad_vocoder_process(ad_vocoder* f, const double* modulator, const double* car
 
 int ad_vocoder_process_device(ad_vocoder* f, const double* d_mod, int64_t ms, const double* d_car, int64_t cs,
                               double* d_out, int64_t os, int64_t n, void* stream) {
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null vocoder handle");
+  return with_handle(f, [&] {
     if (n < 0 || (n > 0 && (!d_mod || !d_car || !d_out || ms < n || cs < n || os < n)))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "bad buffer geometry");
     if (n == 0) return;
@@ -425,27 +380,18 @@ int ad_vocoder_process_device(ad_vocoder* f, const double* d_mod, int64_t ms, co
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "vocoder: out overlaps the modulator without being it");
     if (!(d_out == d_car && os == cs) && overlap(d_out, os, d_car, cs, f->channels, n))
       AD_FAIL(AD_ERR_INVALID_ARGUMENT, "vocoder: out overlaps the carrier without being it");
-    DeviceScope ds(f->device);
     run(f, d_mod, ms, d_car, cs, d_out, os, n, reinterpret_cast<hipStream_t>(stream));
   });
 }
 
 int ad_vocoder_reset(ad_vocoder* f) {
   // Reset :648-670: the envelopes, every section, the counter; ordered after the last call
-  return guard([&] {
-    if (!f) AD_FAIL(AD_ERR_INVALID_ARGUMENT, "null vocoder handle");
-    DeviceScope ds(f->device);
+  return with_handle(f, [&] {
     clear_rows(f, 0, VOC_STATE_ROWS);
     f->counter = 0;
   });
 }
 
-void ad_vocoder_destroy(ad_vocoder* f) {
-  if (!f) return;
-  (void)guard([&] {
-    DeviceScope ds(f->device);
-    delete f;
-  });
-}
+void ad_vocoder_destroy(ad_vocoder* f) { destroy_handle(f); }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Call ordering and the ping-pong delay line shared by the handles that may be
-// called on any stream (ad_conv, ad_fir, ad_resampler, ad_fdn, ad_delay, ad_flanger).
+// called on any stream (ad_conv, ad_fir, ad_resampler and every effect handle of fx_handle.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -54,6 +54,24 @@ struct StreamOrder {
  private:
   void ensure() {
     if (!done) AD_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+  }
+};
+
+// One call of a handle on stream s: enter(s) now, leave(s) when the scope ends, by an exception too, so
+// that what was enqueued before a failure is still covered by the event the next call waits for.  Every
+// run function of an effect handle opens one after its early returns (a call that enqueues nothing does
+// not count as a call); a hand-written enter / leave pair would skip leave on a throw in between.
+struct CallScope {
+  StreamOrder& calls;
+  hipStream_t s;
+  CallScope(StreamOrder& c, hipStream_t stream) : calls(c), s(stream) { calls.enter(s); }
+  CallScope(const CallScope&) = delete;
+  CallScope& operator=(const CallScope&) = delete;
+  ~CallScope() {
+    try {
+      calls.leave(s);
+    } catch (...) {  // the call's own error, if any, is the one to report
+    }
   }
 };
 
