@@ -264,6 +264,30 @@ def lib() -> C.CDLL:
 
 _NEWEST = ("ad_conv_multi_set_long_blocks", "ad_conv_multi_get_long_blocks")
 
+# the effect handles whose create takes a config structure (csrc/fx_handle.hpp): a new kind is one entry here
+_HANDLE_KINDS = (("fdn", FdnConfig), ("delay", DelayConfig), ("flanger", FlangerConfig), ("phaser", PhaserConfig),
+                 ("tremolo", TremoloConfig), ("ringmod", RingModConfig), ("distortion", DistortionConfig),
+                 ("bitcrusher", BitCrusherConfig), ("transient", TransientConfig), ("deesser", DeEsserConfig),
+                 ("lookahead", LookaheadConfig), ("vocoder", VocoderConfig), ("specfreeze", SpecFreezeConfig),
+                 ("pitchspec", PitchSpecConfig))
+
+
+def _handle_prototypes(kind: str, cfg) -> dict:
+    """The prototypes every kind of _HANDLE_KINDS has, {ad_<kind>_<name>: (restype, argtypes)}."""
+    vp, i64, cp = C.c_void_p, C.c_int64, C.POINTER(cfg)
+    common = {
+        "default_config": (None, [cp, C.c_double]),
+        "validate": (C.c_int, [cp]),
+        "create": (C.c_int, [cp, C.c_int, C.c_int, C.POINTER(vp)]),
+        "set_param": (C.c_int, [vp, C.c_int, C.c_double]),
+        "get_config": (C.c_int, [vp, cp]),
+        "process": (C.c_int, [vp, c_double_p, i64]),
+        "process_device": (C.c_int, [vp, vp, i64, i64, vp]),
+        "reset": (C.c_int, [vp]),
+        "destroy": (None, [vp]),
+    }
+    return {f"ad_{kind}_{name}": proto for name, proto in common.items()}
+
 
 def _declare(L: C.CDLL) -> None:
     vp = C.c_void_p
@@ -381,40 +405,13 @@ def _declare(L: C.CDLL) -> None:
         "ad_resampler_kernel_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                                C.POINTER(C.c_int), C.POINTER(C.c_int), c_int64_p]),
         "ad_resampler_destroy": (None, [vp]),
-        "ad_fdn_default_config": (None, [C.POINTER(FdnConfig), C.c_double]),
-        "ad_fdn_validate": (C.c_int, [C.POINTER(FdnConfig)]),
-        "ad_fdn_create": (C.c_int, [C.POINTER(FdnConfig), C.c_int, C.c_int, C.POINTER(vp)]),
-        "ad_fdn_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
-        "ad_fdn_get_config": (C.c_int, [vp, C.POINTER(FdnConfig)]),
         "ad_fdn_derived": (C.c_int, [vp, c_double_p, c_int64_p, c_int64_p, c_double_p]),
         "ad_fdn_kernel_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-        "ad_fdn_process": (C.c_int, [vp, c_double_p, i64]),
-        "ad_fdn_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
-        "ad_fdn_reset": (C.c_int, [vp]),
-        "ad_fdn_destroy": (None, [vp]),
-        "ad_delay_default_config": (None, [C.POINTER(DelayConfig), C.c_double]),
-        "ad_delay_validate": (C.c_int, [C.POINTER(DelayConfig)]),
-        "ad_delay_create": (C.c_int, [C.POINTER(DelayConfig), C.c_int, C.c_int, C.POINTER(vp)]),
-        "ad_delay_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
-        "ad_delay_get_config": (C.c_int, [vp, C.POINTER(DelayConfig)]),
         "ad_delay_derived": (C.c_int, [vp, c_double_p, c_double_p, c_int64_p, c_int64_p]),
         "ad_delay_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 4),
         "ad_delay_set_regime": (C.c_int, [vp, C.c_int]),
-        "ad_delay_process": (C.c_int, [vp, c_double_p, i64]),
-        "ad_delay_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
-        "ad_delay_reset": (C.c_int, [vp]),
-        "ad_delay_destroy": (None, [vp]),
-        "ad_flanger_default_config": (None, [C.POINTER(FlangerConfig), C.c_double]),
-        "ad_flanger_validate": (C.c_int, [C.POINTER(FlangerConfig)]),
-        "ad_flanger_create": (C.c_int, [C.POINTER(FlangerConfig), C.c_int, C.c_int, C.POINTER(vp)]),
-        "ad_flanger_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
-        "ad_flanger_get_config": (C.c_int, [vp, C.POINTER(FlangerConfig)]),
         "ad_flanger_derived": (C.c_int, [vp, c_int64_p, c_int64_p, c_int64_p, c_double_p]),
         "ad_flanger_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 4),
-        "ad_flanger_process": (C.c_int, [vp, c_double_p, i64]),
-        "ad_flanger_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
-        "ad_flanger_reset": (C.c_int, [vp]),
-        "ad_flanger_destroy": (None, [vp]),
         "ad_fx_graph_create_ext": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
         "ad_phaser_set_range": (C.c_int, [vp, C.c_double, C.c_double]),
         "ad_phaser_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
@@ -439,33 +436,19 @@ def _declare(L: C.CDLL) -> None:
         "ad_deesser_reset_metrics": (C.c_int, [vp]),
         "ad_deesser_gain": (C.c_int, [vp, c_double_p, c_double_p, i64]),
         "ad_fx_chain_reset_compressor_metrics": (C.c_int, [vp]),
-        "ad_lookahead_default_config": (None, [C.POINTER(LookaheadConfig), C.c_double]),
-        "ad_lookahead_validate": (C.c_int, [C.POINTER(LookaheadConfig)]),
         "ad_lookahead_derived": (C.c_int, [C.POINTER(LookaheadConfig), c_double_p, c_double_p, c_double_p, c_int64_p]),
-        "ad_lookahead_create": (C.c_int, [C.POINTER(LookaheadConfig), C.c_int, C.c_int, C.POINTER(vp)]),
-        "ad_lookahead_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
-        "ad_lookahead_get_config": (C.c_int, [vp, C.POINTER(LookaheadConfig)]),
         "ad_lookahead_get_state": (C.c_int, [vp, C.c_int, c_double_p]),
         "ad_lookahead_gain": (C.c_int, [vp, c_double_p, c_double_p, i64]),
         "ad_lookahead_last_envelope": (C.c_int, [vp, c_double_p, i64]),
         "ad_lookahead_process": (C.c_int, [vp, c_double_p, c_double_p, i64, i64]),
         "ad_lookahead_process_device": (C.c_int, [vp, vp, i64, vp, i64, i64, i64, vp]),
-        "ad_lookahead_reset": (C.c_int, [vp]),
-        "ad_lookahead_destroy": (None, [vp]),
-        "ad_vocoder_default_config": (None, [C.POINTER(VocoderConfig), C.c_double]),
-        "ad_vocoder_validate": (C.c_int, [C.POINTER(VocoderConfig)]),
         "ad_vocoder_derived": (C.c_int, [C.POINTER(VocoderConfig), C.POINTER(VocoderTables)]),
-        "ad_vocoder_create": (C.c_int, [C.POINTER(VocoderConfig), C.c_int, C.c_int, C.POINTER(vp)]),
-        "ad_vocoder_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
-        "ad_vocoder_get_config": (C.c_int, [vp, C.POINTER(VocoderConfig)]),
         "ad_vocoder_num_bands": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "ad_vocoder_downsample_factors": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
         "ad_vocoder_kernel_info": (C.c_int, [vp] + [C.POINTER(C.c_int)] * 3),
         "ad_vocoder_get_state": (C.c_int, [vp, C.c_int, c_double_p, C.POINTER(C.c_int)]),
         "ad_vocoder_process": (C.c_int, [vp, c_double_p, c_double_p, c_double_p, i64]),
         "ad_vocoder_process_device": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, i64, vp]),
-        "ad_vocoder_reset": (C.c_int, [vp]),
-        "ad_vocoder_destroy": (None, [vp]),
         "ad_xover_validate": (C.c_int, [c_double_p, C.c_int, C.c_int, C.c_double]),
         "ad_xover_sections": (C.c_int, [c_double_p, C.c_int, C.c_int, C.c_double, c_double_p, i64,
                                         C.POINTER(C.c_int)]),
@@ -505,47 +488,15 @@ def _declare(L: C.CDLL) -> None:
                                     c_int64_p, C.c_int]),
         "ad_inverse_filter": (C.c_int, [c_double_p, i64, i64, C.c_double, c_double_p, C.c_int]),
     }
-    for kind, cfg in (("phaser", PhaserConfig), ("tremolo", TremoloConfig), ("ringmod", RingModConfig)):
-        sig.update({  # the three modulation handles share their prototypes
-            f"ad_{kind}_default_config": (None, [C.POINTER(cfg), C.c_double]),
-            f"ad_{kind}_validate": (C.c_int, [C.POINTER(cfg)]),
-            f"ad_{kind}_create": (C.c_int, [C.POINTER(cfg), C.c_int, C.c_int, C.POINTER(vp)]),
-            f"ad_{kind}_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
-            f"ad_{kind}_get_config": (C.c_int, [vp, C.POINTER(cfg)]),
-            f"ad_{kind}_peek_lfo": (C.c_int, [vp, i64, c_double_p, c_double_p]),
-            f"ad_{kind}_process": (C.c_int, [vp, c_double_p, i64]),
-            f"ad_{kind}_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
-            f"ad_{kind}_reset": (C.c_int, [vp]),
-            f"ad_{kind}_destroy": (None, [vp]),
-        })
-    for kind, cfg in (("distortion", DistortionConfig), ("bitcrusher", BitCrusherConfig),
-                      ("transient", TransientConfig), ("deesser", DeEsserConfig)):
-        sig.update({  # the waveshaping and the newer dynamics handles share these prototypes
-            f"ad_{kind}_default_config": (None, [C.POINTER(cfg), C.c_double]),
-            f"ad_{kind}_validate": (C.c_int, [C.POINTER(cfg)]),
-            f"ad_{kind}_create": (C.c_int, [C.POINTER(cfg), C.c_int, C.c_int, C.POINTER(vp)]),
-            f"ad_{kind}_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
-            f"ad_{kind}_get_config": (C.c_int, [vp, C.POINTER(cfg)]),
-            f"ad_{kind}_process": (C.c_int, [vp, c_double_p, i64]),
-            f"ad_{kind}_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
-            f"ad_{kind}_reset": (C.c_int, [vp]),
-            f"ad_{kind}_destroy": (None, [vp]),
-        })
-    for kind, cfg in (("specfreeze", SpecFreezeConfig), ("pitchspec", PitchSpecConfig)):
-        sig.update({  # the two STFT handles share these prototypes
-            f"ad_{kind}_default_config": (None, [C.POINTER(cfg), C.c_double]),
-            f"ad_{kind}_validate": (C.c_int, [C.POINTER(cfg)]),
-            f"ad_{kind}_create": (C.c_int, [C.POINTER(cfg), C.c_int, C.c_int, C.POINTER(vp)]),
-            f"ad_{kind}_set_param": (C.c_int, [vp, C.c_int, C.c_double]),
-            f"ad_{kind}_set_frame": (C.c_int, [vp, C.c_int, c_double_p]),
-            f"ad_{kind}_set_window": (C.c_int, [vp, C.c_int, c_double_p]),
-            f"ad_{kind}_get_config": (C.c_int, [vp, C.POINTER(cfg)]),
-            f"ad_{kind}_process": (C.c_int, [vp, c_double_p, i64]),
-            f"ad_{kind}_process_device": (C.c_int, [vp, vp, i64, i64, vp]),
-            f"ad_{kind}_reset": (C.c_int, [vp]),
-            f"ad_{kind}_profile": (C.c_int, [vp, C.c_int, c_double_p]),
-            f"ad_{kind}_destroy": (None, [vp]),
-        })
+    for kind in ("phaser", "tremolo", "ringmod"):
+        sig[f"ad_{kind}_peek_lfo"] = (C.c_int, [vp, i64, c_double_p, c_double_p])
+    for kind in ("specfreeze", "pitchspec"):
+        sig[f"ad_{kind}_set_frame"] = (C.c_int, [vp, C.c_int, c_double_p])
+        sig[f"ad_{kind}_set_window"] = (C.c_int, [vp, C.c_int, c_double_p])
+        sig[f"ad_{kind}_profile"] = (C.c_int, [vp, C.c_int, c_double_p])
+    for kind, cfg in _HANDLE_KINDS:
+        for name, proto in _handle_prototypes(kind, cfg).items():
+            sig.setdefault(name, proto)  # lookahead's and vocoder's own process / process_device above stand
     # an older build selected through ALGODSP_LIB (A/B runs against a parent
     # commit's library) may lack the entry points named in _NEWEST: those stay
     # unbound and raise AttributeError when called.  Any other missing symbol

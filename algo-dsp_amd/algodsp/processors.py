@@ -28,6 +28,12 @@ like the reference's own tests:
 Every instance can carry `channels` independent reference instances (one
 lane each on the GPU); buffers are [channels][n] float64 (a 1-D buffer is
 one channel).  All work runs in libalgodsp_hip.so; there is no CPU path.
+
+Every class that owns a C handle derives from _Handle, which names the
+entry points ad_<kind>_* and owns the handle's life.  The fourteen effects
+whose create takes a config structure derive from _ConfigHandle: a class
+there is its `_kind`, its `_config` structure, its option names, its P_*
+parameter numbers and a table of setters and getters (_setter, _getter).
 """
 from __future__ import annotations
 
@@ -42,6 +48,7 @@ from ._lib import (AD_ERR_INVALID_ARGUMENT, BitCrusherConfig, CompressorConfig, 
 
 DEVICE = 0
 SEC_STRIDE = 6  # {pre_gain, b0, b1, b2, a1, a2}
+_INT, _I64, _F64 = (C.c_int,), (C.c_int64,), (C.c_double,)  # the C types of by-reference outputs, for _outputs
 
 
 def _as2d(buf, channels: int):
@@ -63,22 +70,132 @@ def section_table(coeffs, gain: float = 1.0) -> np.ndarray:
     return t
 
 
-class _FxChain:
-    def __init__(self, channels: int, device: int):
+def _outputs(fn, types, *args):
+    """fn(*args, out...) with one by-reference output of each C type in `types`: the values it wrote."""
+    outs = [t() for t in types]
+    check(fn(*args, *[C.byref(o) for o in outs]))
+    return tuple(o.value for o in outs)
+
+
+def _setter(param):
+    """A method that forwards its value to set_param: `param` is the P_* number, or the constant's name in
+    a base whose subclasses number it differently."""
+    def set_(self, v):
+        self._set(getattr(self, param) if isinstance(param, str) else param, v)
+    return set_
+
+
+def _getter(field: str, kind=None):
+    """A method that returns `field` of config(), through `kind` (bool, for a flag) when given."""
+    def get(self):
+        v = getattr(self.config(), field)
+        return v if kind is None else kind(v)
+    return get
+
+
+class _Handle:
+    """A C handle whose entry points are named ad_<kind>_*: create (whatever comes before channels, device
+    and the handle goes through _create), process, process_device, reset and destroy."""
+
+    _kind = ""
+
+    @classmethod
+    def _fn(cls, name):
+        return getattr(lib(), f"ad_{cls._kind}_{name}")
+
+    def _create(self, channels: int, device: int, *head):
         self.channels = int(channels)
         self._h = C.c_void_p()
-        check(lib().ad_fx_chain_create(self.channels, int(device), C.byref(self._h)))
+        self._device_fn = self._fn("process_device")  # bound once: the call that streaming callers repeat
+        check(self._fn("create")(*head, self.channels, int(device), C.byref(self._h)))
+
+    def _out(self, name, types, *args):
+        """ad_<kind>_<name>(handle, *args, out...): the values of the by-reference outputs."""
+        return _outputs(self._fn(name), types, self._h, *args)
 
     def _process(self, buf):
         b = _as2d(buf, self.channels)
-        check(lib().ad_fx_chain_process(self._h, ptr(b), b.shape[1]))
+        check(self._fn("process")(self._h, ptr(b), b.shape[1]))
 
     def process_device(self, d_buf: int, stride: int, n: int, stream: int | None = None):
-        check(lib().ad_fx_chain_process_device(self._h, C.c_void_p(d_buf), int(stride), int(n),
-                                               C.c_void_p(stream or 0)))
+        check(self._device_fn(self._h, C.c_void_p(d_buf), int(stride), int(n), C.c_void_p(stream or 0)))
 
     def Reset(self):
-        check(lib().ad_fx_chain_reset(self._h))
+        check(self._fn("reset")(self._h))
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _ConfigHandle(_Handle):
+    """A handle whose create takes a config structure: the constructor, options as keywords, set_param and
+    get_config, once for the fourteen effect classes.  A class names its structure (`_config`), the option
+    keywords stored as floats (`_options`), whole numbers (`_int_options`) and flags (`_bool_options`), and
+    what the "unknown option" error calls it (`_name`)."""
+
+    _config = None
+    _name = ""
+    _options = ()
+    _int_options = ()
+    _bool_options = ()
+
+    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
+        cfg = self._make_config(sample_rate, config, **options)
+        self._create(channels, device, C.byref(cfg))
+
+    @classmethod
+    def _make_config(cls, sample_rate, config=None, **options):
+        """The structure the constructor passes to create: default_config(sample_rate), or a copy of `config`,
+        with the options stored.  An unknown option raises before any library call; nothing here needs a
+        device."""
+        unknown = set(options) - set(cls._options + cls._int_options + cls._bool_options)
+        if unknown:
+            raise TypeError(f"unknown {cls._name} option {min(unknown)!r}")
+        cfg = cls._config()
+        if config is None:
+            cls._fn("default_config")(C.byref(cfg), float(sample_rate))
+        else:
+            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
+        for k, v in options.items():
+            cls._option(cfg, k, v)
+        return cfg
+
+    @classmethod
+    def _option(cls, cfg, key, value):
+        """Stores one option keyword; a class overrides it for an option that is more than one field."""
+        if key in cls._bool_options:
+            setattr(cfg, key, 1 if value else 0)
+        else:
+            setattr(cfg, key, int(value) if key in cls._int_options else float(value))
+
+    def _set(self, which: int, v):
+        check(self._fn("set_param")(self._h, which, float(v)))
+
+    def config(self):
+        cfg = self._config()
+        check(self._fn("get_config")(self._h, C.byref(cfg)))
+        return cfg
+
+    def ProcessInPlace(self, buf):
+        self._process(buf)
+
+    SetSampleRate = _setter(0)  # parameter 0 of every kind
+    SampleRate = _getter("sample_rate")
+
+
+class _FxChain(_Handle):
+    _kind = "fx_chain"
+
+    def __init__(self, channels: int, device: int):
+        self._create(channels, device)
 
     # engine selection (include/algodsp.h ad_fx_chain_set_engine); the fused
     # and staged engines give identical results, the time-parallel one within
@@ -91,20 +208,7 @@ class _FxChain:
     def LastEngine(self) -> tuple[int, float]:
         """(engine that ran the last call, the EQ's round-off noise estimate)
         (ad_fx_chain_last_engine)."""
-        e, ng = C.c_int(), C.c_double()
-        check(lib().ad_fx_chain_last_engine(self._h, C.byref(e), C.byref(ng)))
-        return e.value, ng.value
-
-    def close(self):
-        if self._h:
-            lib().ad_fx_chain_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._out("last_engine", _INT + _F64)
 
 
 class Chain(_FxChain):
@@ -154,8 +258,34 @@ def Section(b0, b1, b2, a1, a2, channels: int = 1, device: int = DEVICE) -> Chai
     return Chain([[b0, b1, b2, a1, a2]], 1.0, channels, device)
 
 
+def _flag(on) -> int:
+    return int(bool(on))
+
+
+# The setters of a compressor's config, as Compressor.Set<name>(v) (compressor.go:130-305, core.go:106-250) and
+# as MultibandCompressor.SetBand<name>(band, v) (multiband.go:190-329) and SetAllBands<name>(v) (:331-437):
+# (name, config field, what the value goes through, the fields stored with it, has a SetAllBands form)
+_DYNAMICS_SETTERS = (
+    ("Threshold", "threshold_db", float, {}, True),
+    ("Ratio", "ratio", float, {}, True),
+    ("Knee", "knee_db", float, {}, True),
+    ("Attack", "attack_ms", float, {}, True),
+    ("Release", "release_ms", float, {}, True),
+    ("RMSWindow", "rms_window_ms", float, {}, True),
+    ("SidechainLowCut", "sidechain_low_cut_hz", float, {}, False),
+    ("SidechainHighCut", "sidechain_high_cut_hz", float, {}, False),
+    ("AutoMakeup", "auto_makeup", _flag, {}, False),
+    ("MakeupGain", "makeup_db", float, {"auto_makeup": 0}, False),  # SetManualMakeupGain (core.go:201-210,
+                                                                    # multiband.go:242-249) turns auto makeup off
+    ("Topology", "topology", int, {}, True),  # core.go:106-114
+    ("DetectorMode", "detector_mode", int, {}, True),  # core.go:116-124
+    ("FeedbackRatioScale", "feedback_ratio_scale", _flag, {}, True),  # core.go:126-129
+)
+
+
 class Compressor(_FxChain):
-    """dynamics.Compressor (compressor.go:39-431) on `channels` lanes."""
+    """dynamics.Compressor (compressor.go:39-431) on `channels` lanes.  Its setters are Set<name> for every
+    name of _DYNAMICS_SETTERS."""
 
     def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, **cfg):
         super().__init__(channels, device)
@@ -181,53 +311,21 @@ class Compressor(_FxChain):
                 setattr(self.cfg, k, v)
             raise
 
-    # setters (compressor.go:130-305, core.go:131-250)
-    def SetThreshold(self, db):
-        self._set(threshold_db=db)
-
-    def SetRatio(self, r):
-        self._set(ratio=r)
-
-    def SetKnee(self, db):
-        self._set(knee_db=db)
-
-    def SetAttack(self, ms):
-        self._set(attack_ms=ms)
-
-    def SetRelease(self, ms):
-        self._set(release_ms=ms)
-
-    def SetRMSWindow(self, ms):
-        self._set(rms_window_ms=ms)
-
-    def SetSidechainLowCut(self, hz):
-        self._set(sidechain_low_cut_hz=hz)
-
-    def SetSidechainHighCut(self, hz):
-        self._set(sidechain_high_cut_hz=hz)
-
-    def SetAutoMakeup(self, on: bool):
-        self._set(auto_makeup=int(bool(on)))
-
-    def SetMakeupGain(self, db):  # SetManualMakeupGain (core.go:201-210) turns auto makeup off
-        self._set(makeup_db=db, auto_makeup=0)
-
-    def SetTopology(self, topology: int):  # core.go:106-114
-        self._set(topology=int(topology))
-
-    def SetDetectorMode(self, mode: int):  # core.go:116-124
-        self._set(detector_mode=int(mode))
-
-    def SetFeedbackRatioScale(self, on: bool):  # core.go:126-129
-        self._set(feedback_ratio_scale=int(bool(on)))
-
     def ProcessInPlace(self, buf):  # compressor.go:362-366
         self._process(buf)
 
     def Metrics(self, channel: int = 0):
-        ip, op, gr = C.c_double(), C.c_double(), C.c_double()
-        check(lib().ad_fx_chain_compressor_metrics(self._h, int(channel), C.byref(ip), C.byref(op), C.byref(gr)))
-        return ip.value, op.value, gr.value
+        return self._out("compressor_metrics", _F64 * 3, int(channel))
+
+
+def _compressor_setter(field, kind, also):
+    def set_(self, v):
+        self._set(**{field: kind(v)}, **also)
+    return set_
+
+
+for _name, _field, _kind, _also, _ in _DYNAMICS_SETTERS:
+    setattr(Compressor, "Set" + _name, _compressor_setter(_field, _kind, _also))
 
 
 class Expander(Compressor):
@@ -277,6 +375,13 @@ class Gate(Expander):
         self._set_attr("hold_ms", ms)
 
 
+def _reverb_setter(attr):
+    def set_(self, v):
+        setattr(self, attr, float(v))
+        self._apply()
+    return set_
+
+
 class Reverb(_FxChain):
     """reverb.Reverb (Freeverb, reverb.go:33-235) with NewReverb defaults."""
 
@@ -288,31 +393,17 @@ class Reverb(_FxChain):
     def _apply(self):
         check(lib().ad_fx_chain_set_freeverb(self._h, self.wet, self.dry, self.room, self.damp, self.gain))
 
-    def SetWet(self, v):
-        self.wet = float(v)
-        self._apply()
-
-    def SetDry(self, v):
-        self.dry = float(v)
-        self._apply()
-
-    def SetRoomSize(self, v):
-        self.room = float(v)
-        self._apply()
-
-    def SetDamp(self, v):
-        self.damp = float(v)
-        self._apply()
-
-    def SetGain(self, v):
-        self.gain = float(v)
-        self._apply()
+    SetWet = _reverb_setter("wet")  # reverb.go:192-220
+    SetDry = _reverb_setter("dry")
+    SetRoomSize = _reverb_setter("room")
+    SetDamp = _reverb_setter("damp")
+    SetGain = _reverb_setter("gain")
 
     def ProcessInPlace(self, buf):  # reverb.go:185-189
         self._process(buf)
 
 
-class FDNReverb:
+class FDNReverb(_ConfigHandle):
     """reverb.FDNReverb (fdn_reverb.go:37-391) for `channels` instances sharing
     one configuration: NewFDNReverb(sample_rate), or `config` (an FdnConfig)
     applied whole.  The setters are the reference's, side effects included
@@ -320,72 +411,29 @@ class FDNReverb:
     nothing."""
 
     P_SAMPLE_RATE, P_WET, P_DRY, P_RT60, P_DAMP, P_PRE_DELAY, P_MOD_DEPTH, P_MOD_RATE = range(8)  # AD_FDN_*
+    _kind = "fdn"
+    _name = "fdn reverb"
+    _config = FdnConfig
 
     def __init__(self, sample_rate: float = 44100.0, channels: int = 1, device: int = DEVICE, config=None):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
-        cfg = FdnConfig()
-        if config is None:
-            lib().ad_fdn_default_config(C.byref(cfg), float(sample_rate))
-        else:
-            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        check(lib().ad_fdn_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+        super().__init__(sample_rate, channels, device, config)
 
-    def _set(self, which: int, v):
-        check(lib().ad_fdn_set_param(self._h, which, float(v)))
-
-    def config(self) -> FdnConfig:
-        cfg = FdnConfig()
-        check(lib().ad_fdn_get_config(self._h, C.byref(cfg)))
-        return cfg
-
-    def SetSampleRate(self, v):  # :95-106
-        self._set(self.P_SAMPLE_RATE, v)
-
-    def SetWet(self, v):  # :109-117
-        self._set(self.P_WET, v)
-
-    def SetDry(self, v):  # :120-128
-        self._set(self.P_DRY, v)
-
-    def SetRT60(self, v):  # :131-140
-        self._set(self.P_RT60, v)
-
-    def SetDamp(self, v):  # :143-151
-        self._set(self.P_DAMP, v)
-
-    def SetPreDelay(self, v):  # :154-163
-        self._set(self.P_PRE_DELAY, v)
-
-    def SetModDepth(self, v):  # :166-175
-        self._set(self.P_MOD_DEPTH, v)
-
-    def SetModRate(self, v):  # :178-186
-        self._set(self.P_MOD_RATE, v)
-
-    def SampleRate(self) -> float:  # :251-272
-        return self.config().sample_rate
-
-    def Wet(self) -> float:
-        return self.config().wet
-
-    def Dry(self) -> float:
-        return self.config().dry
-
-    def RT60(self) -> float:
-        return self.config().rt60_seconds
-
-    def Damp(self) -> float:
-        return self.config().damp
-
-    def PreDelay(self) -> float:
-        return self.config().pre_delay_seconds
-
-    def ModDepth(self) -> float:
-        return self.config().mod_depth_seconds
-
-    def ModRate(self) -> float:
-        return self.config().mod_rate_hz
+    SetSampleRate = _setter(P_SAMPLE_RATE)  # :95-106
+    SetWet = _setter(P_WET)  # :109-117
+    SetDry = _setter(P_DRY)  # :120-128
+    SetRT60 = _setter(P_RT60)  # :131-140
+    SetDamp = _setter(P_DAMP)  # :143-151
+    SetPreDelay = _setter(P_PRE_DELAY)  # :154-163
+    SetModDepth = _setter(P_MOD_DEPTH)  # :166-175
+    SetModRate = _setter(P_MOD_RATE)  # :178-186
+    SampleRate = _getter("sample_rate")  # :251-272
+    Wet = _getter("wet")
+    Dry = _getter("dry")
+    RT60 = _getter("rt60_seconds")
+    Damp = _getter("damp")
+    PreDelay = _getter("pre_delay_seconds")
+    ModDepth = _getter("mod_depth_seconds")
+    ModRate = _getter("mod_rate_hz")
 
     def derived(self):
         """(feedback gains [8], line lengths [8], pre-delay line length, LFO
@@ -393,70 +441,16 @@ class FDNReverb:
         phase after the last call (ad_fdn_derived)."""
         g = np.zeros(8)
         ln = np.zeros(8, dtype=np.int64)
-        pl, ph = C.c_int64(), C.c_double()
-        check(lib().ad_fdn_derived(self._h, ptr(g), ln.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(pl),
-                                   C.byref(ph)))
-        return g, ln, pl.value, ph.value
+        return (g, ln) + self._out("derived", _I64 + _F64, ptr(g), ln.ctypes.data_as(C.POINTER(C.c_int64)))
 
     def kernel_info(self):
         """(block, sub_block, lds_bytes) of ad_fdn_kernel_info."""
-        a, b, c = C.c_int(), C.c_int(), C.c_int()
-        check(lib().ad_fdn_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return a.value, b.value, c.value
+        return self._out("kernel_info", _INT * 3)
 
-    def ProcessInPlace(self, buf):  # :244-248
-        b = _as2d(buf, self.channels)
-        check(lib().ad_fdn_process(self._h, ptr(b), b.shape[1]))
-
-    def process_device(self, d_buf: int, stride: int, n: int, stream: int | None = None):
-        check(lib().ad_fdn_process_device(self._h, C.c_void_p(d_buf), int(stride), int(n), C.c_void_p(stream or 0)))
-
-    def Reset(self):  # :189-197
-        check(lib().ad_fdn_reset(self._h))
-
-    def close(self):
-        if self._h:
-            lib().ad_fdn_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    # ProcessInPlace :244-248, Reset :189-197
 
 
-class _Handle:
-    """A C handle with process / process_device / reset / destroy named ad_<kind>_*."""
-
-    _kind = ""
-
-    def _fn(self, name):
-        return getattr(lib(), f"ad_{self._kind}_{name}")
-
-    def ProcessInPlace(self, buf):
-        b = _as2d(buf, self.channels)
-        check(self._fn("process")(self._h, ptr(b), b.shape[1]))
-
-    def process_device(self, d_buf: int, stride: int, n: int, stream: int | None = None):
-        check(self._fn("process_device")(self._h, C.c_void_p(d_buf), int(stride), int(n), C.c_void_p(stream or 0)))
-
-    def Reset(self):
-        check(self._fn("reset")(self._h))
-
-    def close(self):
-        if self._h:
-            self._fn("destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Delay(_Handle):
+class Delay(_ConfigHandle):
     """effects.Delay (delay.go:25-257) for `channels` instances sharing one
     configuration: NewDelay(sample_rate), or `config` (a DelayConfig) as
     ad_delay_create applies it (NewDelay, then SetTargetTime, SetFeedback,
@@ -465,79 +459,41 @@ class Delay(_Handle):
 
     P_SAMPLE_RATE, P_TIME, P_FEEDBACK, P_MIX, P_TARGET_TIME, P_SAMPLES, P_SMOOTH_COEFF = range(7)  # AD_DELAY_*
     _kind = "delay"
+    _name = "delay"
+    _config = DelayConfig
 
     def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
-        cfg = DelayConfig()
-        if config is None:
-            lib().ad_delay_default_config(C.byref(cfg), float(sample_rate))
-        else:
-            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        check(lib().ad_delay_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+        super().__init__(sample_rate, channels, device, config)
 
-    def _set(self, which: int, v):
-        check(lib().ad_delay_set_param(self._h, which, float(v)))
-
-    def config(self) -> DelayConfig:
-        cfg = DelayConfig()
-        check(lib().ad_delay_get_config(self._h, C.byref(cfg)))
-        return cfg
-
-    def SetSampleRate(self, v):  # :63-72
-        self._set(self.P_SAMPLE_RATE, v)
-
-    def SetTime(self, v):  # :77-89
-        self._set(self.P_TIME, v)
-
-    def SetTargetTime(self, v):  # :95-106
-        self._set(self.P_TARGET_TIME, v)
-
-    def SetFeedback(self, v):  # :109-117
-        self._set(self.P_FEEDBACK, v)
-
-    def SetMix(self, v):  # :120-128
-        self._set(self.P_MIX, v)
-
-    def SetDelaySamples(self, v):  # mode 1: simpleDelayRuntime.Configure
-        self._set(self.P_SAMPLES, v)
-
-    def SetSmoothCoeff(self, v):  # smoothCoeff, for a caller whose exp is not the C library's
-        self._set(self.P_SMOOTH_COEFF, v)
-
-    def SampleRate(self) -> float:  # :176-185
-        return self.config().sample_rate
-
-    def Time(self) -> float:
-        return self.config().time_seconds
-
-    def Feedback(self) -> float:
-        return self.config().feedback
-
-    def Mix(self) -> float:
-        return self.config().mix
+    SetSampleRate = _setter(P_SAMPLE_RATE)  # :63-72
+    SetTime = _setter(P_TIME)  # :77-89
+    SetTargetTime = _setter(P_TARGET_TIME)  # :95-106
+    SetFeedback = _setter(P_FEEDBACK)  # :109-117
+    SetMix = _setter(P_MIX)  # :120-128
+    SetDelaySamples = _setter(P_SAMPLES)  # mode 1: simpleDelayRuntime.Configure
+    SetSmoothCoeff = _setter(P_SMOOTH_COEFF)  # smoothCoeff, for a caller whose exp is not the C library's
+    SampleRate = _getter("sample_rate")  # :176-185
+    Time = _getter("time_seconds")
+    Feedback = _getter("feedback")
+    Mix = _getter("mix")
 
     def derived(self):
         """(currentSamples, targetSamples, ring length, write position) of ad_delay_derived."""
-        c, t, ln, wp = C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
-        check(lib().ad_delay_derived(self._h, C.byref(c), C.byref(t), C.byref(ln), C.byref(wp)))
-        return c.value, t.value, ln.value, wp.value
+        return self._out("derived", _F64 * 2 + _I64 * 2)
 
     def CurrentDelaySamples(self) -> float:  # :189
         return self.derived()[0]
 
     def kernel_info(self):
         """(block, sub_block, regime of the last call, its launches) of ad_delay_kernel_info."""
-        v = [C.c_int() for _ in range(4)]
-        check(lib().ad_delay_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._out("kernel_info", _INT * 4)
 
     def set_regime(self, regime: int):
         """0: the library chooses; 1: one launch per block; 2: one persistent launch."""
         check(lib().ad_delay_set_regime(self._h, int(regime)))
 
 
-class Flanger(_Handle):
+class Flanger(_ConfigHandle):
     """modulation.Flanger (flanger.go:108-424) for `channels` instances sharing
     one configuration: NewFlanger(sample_rate, options...) with the options as
     keywords (rate_hz, depth_seconds, base_delay_seconds, feedback, mix), or
@@ -545,106 +501,35 @@ class Flanger(_Handle):
 
     P_SAMPLE_RATE, P_RATE, P_DEPTH, P_BASE_DELAY, P_FEEDBACK, P_MIX = range(6)  # AD_FLANGER_*
     _kind = "flanger"
+    _name = "flanger"
+    _config = FlangerConfig
+    _options = ("rate_hz", "depth_seconds", "base_delay_seconds", "feedback", "mix")
 
-    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
-        cfg = FlangerConfig()
-        if config is None:
-            lib().ad_flanger_default_config(C.byref(cfg), float(sample_rate))
-        else:
-            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        for k, v in options.items():
-            if k not in ("rate_hz", "depth_seconds", "base_delay_seconds", "feedback", "mix"):
-                raise TypeError(f"unknown flanger option {k!r}")
-            setattr(cfg, k, float(v))
-        check(lib().ad_flanger_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
-
-    def _set(self, which: int, v):
-        check(lib().ad_flanger_set_param(self._h, which, float(v)))
-
-    def config(self) -> FlangerConfig:
-        cfg = FlangerConfig()
-        check(lib().ad_flanger_get_config(self._h, C.byref(cfg)))
-        return cfg
-
-    def SetSampleRate(self, v):  # :165-173
-        self._set(self.P_SAMPLE_RATE, v)
-
-    def SetRateHz(self, v):  # :176-184
-        self._set(self.P_RATE, v)
-
-    def SetDepthSeconds(self, v):  # :187-203
-        self._set(self.P_DEPTH, v)
-
-    def SetBaseDelaySeconds(self, v):  # :206-224
-        self._set(self.P_BASE_DELAY, v)
-
-    def SetFeedback(self, v):  # :227-235
-        self._set(self.P_FEEDBACK, v)
-
-    def SetMix(self, v):  # :238-246
-        self._set(self.P_MIX, v)
-
-    def SampleRate(self) -> float:  # :299-314
-        return self.config().sample_rate
-
-    def RateHz(self) -> float:
-        return self.config().rate_hz
-
-    def DepthSeconds(self) -> float:
-        return self.config().depth_seconds
-
-    def BaseDelaySeconds(self) -> float:
-        return self.config().base_delay_seconds
-
-    def Feedback(self) -> float:
-        return self.config().feedback
-
-    def Mix(self) -> float:
-        return self.config().mix
+    SetSampleRate = _setter(P_SAMPLE_RATE)  # :165-173
+    SetRateHz = _setter(P_RATE)  # :176-184
+    SetDepthSeconds = _setter(P_DEPTH)  # :187-203
+    SetBaseDelaySeconds = _setter(P_BASE_DELAY)  # :206-224
+    SetFeedback = _setter(P_FEEDBACK)  # :227-235
+    SetMix = _setter(P_MIX)  # :238-246
+    SampleRate = _getter("sample_rate")  # :299-314
+    RateHz = _getter("rate_hz")
+    DepthSeconds = _getter("depth_seconds")
+    BaseDelaySeconds = _getter("base_delay_seconds")
+    Feedback = _getter("feedback")
+    Mix = _getter("mix")
 
     def derived(self):
         """(ring length, maxDelay, write position, LFO phase after the last call) of ad_flanger_derived."""
-        ln, md, wp, ph = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double()
-        check(lib().ad_flanger_derived(self._h, C.byref(ln), C.byref(md), C.byref(wp), C.byref(ph)))
-        return ln.value, md.value, wp.value, ph.value
+        return self._out("derived", _I64 * 3 + _F64)
 
     def kernel_info(self):
         """(block, sub_block, channels per workgroup, lds_bytes) of ad_flanger_kernel_info."""
-        v = [C.c_int() for _ in range(4)]
-        check(lib().ad_flanger_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._out("kernel_info", _INT * 4)
 
 
-class _ModHandle(_Handle):
+class _ModHandle(_ConfigHandle):
     """What Phaser, Tremolo and RingModulator share: a config structure whose
-    field k is parameter k, options as keywords, and peek_lfo."""
-
-    _config = None
-    _options = ()
-
-    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
-        cfg = self._config()
-        if config is None:
-            self._fn("default_config")(C.byref(cfg), float(sample_rate))
-        else:
-            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        for k, v in options.items():
-            if k not in self._options:
-                raise TypeError(f"unknown {self._kind} option {k!r}")
-            setattr(cfg, k, int(v) if k == "stages" else float(v))
-        check(self._fn("create")(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
-
-    def _set(self, which: int, v):
-        check(self._fn("set_param")(self._h, which, float(v)))
-
-    def config(self):
-        cfg = self._config()
-        check(self._fn("get_config")(self._h, C.byref(cfg)))
-        return cfg
+    field k is parameter k, a mix, and peek_lfo."""
 
     def peek_lfo(self, n: int):
         """(phases, table) of the next n samples as the kernels would take them:
@@ -654,17 +539,8 @@ class _ModHandle(_Handle):
         check(self._fn("peek_lfo")(self._h, int(n), ptr(ph), ptr(tab)))
         return ph, tab
 
-    def SetSampleRate(self, v):
-        self._set(0, v)
-
-    def SetMix(self, v):
-        self._set(self.P_MIX, v)
-
-    def SampleRate(self) -> float:
-        return self.config().sample_rate
-
-    def Mix(self) -> float:
-        return self.config().mix
+    SetMix = _setter("P_MIX")
+    Mix = _getter("mix")
 
 
 class Phaser(_ModHandle):
@@ -676,79 +552,50 @@ class Phaser(_ModHandle):
 
     P_SAMPLE_RATE, P_RATE, P_MIN_FREQ, P_MAX_FREQ, P_FEEDBACK, P_MIX, P_STAGES = range(7)  # AD_PHASER_*
     _kind = "phaser"
+    _name = "phaser"
     _config = PhaserConfig
-    _options = ("rate_hz", "min_freq_hz", "max_freq_hz", "stages", "feedback", "mix")
+    _options = ("rate_hz", "min_freq_hz", "max_freq_hz", "feedback", "mix")
+    _int_options = ("stages",)
 
-    def SetRateHz(self, v):  # :194-202
-        self._set(self.P_RATE, v)
+    SetRateHz = _setter(P_RATE)  # :194-202
+    SetStages = _setter(P_STAGES)  # :221-233
+    SetFeedback = _setter(P_FEEDBACK)  # :236-244
+    RateHz = _getter("rate_hz")  # :302-320
+    MinFrequencyHz = _getter("min_freq_hz")
+    MaxFrequencyHz = _getter("max_freq_hz")
+    Stages = _getter("stages")
+    Feedback = _getter("feedback")
 
     def SetFrequencyRangeHz(self, min_freq_hz, max_freq_hz):  # :205-218
         check(lib().ad_phaser_set_range(self._h, float(min_freq_hz), float(max_freq_hz)))
 
-    def SetStages(self, v):  # :221-233
-        self._set(self.P_STAGES, v)
-
-    def SetFeedback(self, v):  # :236-244
-        self._set(self.P_FEEDBACK, v)
-
-    def RateHz(self) -> float:  # :302-320
-        return self.config().rate_hz
-
-    def MinFrequencyHz(self) -> float:
-        return self.config().min_freq_hz
-
-    def MaxFrequencyHz(self) -> float:
-        return self.config().max_freq_hz
-
-    def Stages(self) -> int:
-        return self.config().stages
-
-    def Feedback(self) -> float:
-        return self.config().feedback
-
     def kernel_info(self):
         """(channels per workgroup, samples staged per chunk, lds_bytes) of ad_phaser_kernel_info."""
-        v = [C.c_int() for _ in range(3)]
-        check(lib().ad_phaser_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._out("kernel_info", _INT * 3)
 
 
 class Tremolo(_ModHandle):
     """modulation.Tremolo (tremolo.go:86-294): NewTremolo(sample_rate,
     options...) with the options as keywords (rate_hz, depth, smoothing_ms,
-    mix), or `config` (a TremoloConfig) applied whole."""
+    mix, smoothing_coeff), or `config` (a TremoloConfig) applied whole."""
 
     P_SAMPLE_RATE, P_RATE, P_DEPTH, P_SMOOTHING, P_MIX, P_SMOOTHING_COEFF = range(6)  # AD_TREMOLO_*
     _kind = "tremolo"
+    _name = "tremolo"
     _config = TremoloConfig
     _options = ("rate_hz", "depth", "smoothing_ms", "mix", "smoothing_coeff")
 
-    def SetRateHz(self, v):  # :150-158
-        self._set(self.P_RATE, v)
-
-    def SetDepth(self, v):  # :161-169
-        self._set(self.P_DEPTH, v)
-
-    def SetSmoothingMs(self, v):  # :172-181
-        self._set(self.P_SMOOTHING, v)
-
-    def SetSmoothingCoeff(self, v):  # smoothingCoef, for a caller whose exp is not the C library's
-        self._set(self.P_SMOOTHING_COEFF, v)
-
-    def RateHz(self) -> float:  # :233-246
-        return self.config().rate_hz
-
-    def Depth(self) -> float:
-        return self.config().depth
-
-    def SmoothingMs(self) -> float:
-        return self.config().smoothing_ms
+    SetRateHz = _setter(P_RATE)  # :150-158
+    SetDepth = _setter(P_DEPTH)  # :161-169
+    SetSmoothingMs = _setter(P_SMOOTHING)  # :172-181
+    SetSmoothingCoeff = _setter(P_SMOOTHING_COEFF)  # smoothingCoef, for a caller whose exp is not the C library's
+    RateHz = _getter("rate_hz")  # :233-246
+    Depth = _getter("depth")
+    SmoothingMs = _getter("smoothing_ms")
 
     def kernel_info(self):
         """(samples of a row per apply workgroup, the stepper lane's chunk, smoothed) of ad_tremolo_kernel_info."""
-        v = [C.c_int() for _ in range(3)]
-        check(lib().ad_tremolo_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._out("kernel_info", _INT * 3)
 
 
 class RingModulator(_ModHandle):
@@ -758,71 +605,23 @@ class RingModulator(_ModHandle):
 
     P_SAMPLE_RATE, P_CARRIER, P_MIX = range(3)  # AD_RINGMOD_*
     _kind = "ringmod"
+    _name = "ringmod"
     _config = RingModConfig
     _options = ("carrier_hz", "mix")
 
-    def SetCarrierHz(self, v):  # :115-124
-        self._set(self.P_CARRIER, v)
-
-    def CarrierHz(self) -> float:  # :171
-        return self.config().carrier_hz
+    SetCarrierHz = _setter(P_CARRIER)  # :115-124
+    CarrierHz = _getter("carrier_hz")  # :171
 
     def kernel_info(self):
         """(samples of a row per apply workgroup, table threads, phaseInc) of ad_ringmod_kernel_info."""
-        a, b, inc = C.c_int(), C.c_int(), C.c_double()
-        check(lib().ad_ringmod_kernel_info(self._h, C.byref(a), C.byref(b), C.byref(inc)))
-        return a.value, b.value, inc.value
+        return self._out("kernel_info", _INT * 2 + _F64)
 
 
-class _ShaperHandle(_Handle):
-    """What Distortion and BitCrusher share: a config structure, options as
-    keywords, set_param with the int parameters as whole numbers."""
+class _ShaperHandle(_ConfigHandle):
+    """What Distortion and BitCrusher share: a mix."""
 
-    _config = None
-    _options = ()
-    _int_options = ()
-
-    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
-        cfg = self._config()
-        if config is None:
-            self._fn("default_config")(C.byref(cfg), float(sample_rate))
-        else:
-            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        for k, v in options.items():
-            if k == "cheb_weights":
-                w = [float(x) for x in v]
-                if len(w) > 16:
-                    raise TypeError("at most 16 chebyshev weights")
-                cfg.cheb_weights = (C.c_double * 16)(*w)
-            elif k in self._int_options:
-                setattr(cfg, k, int(v))
-            elif k in self._options:
-                setattr(cfg, k, float(v))
-            else:
-                raise TypeError(f"unknown {self._kind} option {k!r}")
-        check(self._fn("create")(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
-
-    def _set(self, which: int, v):
-        check(self._fn("set_param")(self._h, which, float(v)))
-
-    def config(self):
-        cfg = self._config()
-        check(self._fn("get_config")(self._h, C.byref(cfg)))
-        return cfg
-
-    def SetSampleRate(self, v):
-        self._set(0, v)
-
-    def SetMix(self, v):
-        self._set(self.P_MIX, v)
-
-    def SampleRate(self) -> float:
-        return self.config().sample_rate
-
-    def Mix(self) -> float:
-        return self.config().mix
+    SetMix = _setter("P_MIX")
+    Mix = _getter("mix")
 
 
 class Distortion(_ShaperHandle):
@@ -842,42 +641,40 @@ class Distortion(_ShaperHandle):
     APPROX = ("exact", "polynomial")
     HARMONICS = ("all", "odd", "even")
     _kind = "distortion"
+    _name = "distortion"
     _config = DistortionConfig
-    _options = ("drive", "mix", "output_level", "clip_level", "shape", "bias", "cheb_gain")
+    _options = ("drive", "mix", "output_level", "clip_level", "shape", "bias", "cheb_gain", "cheb_weights")
     _int_options = ("mode", "approx", "cheb_order", "cheb_harmonic", "cheb_invert", "cheb_dc_bypass")
 
-    def SetMode(self, v):  # :376-384
-        self._set(self.P_MODE, v)
+    @classmethod
+    def _option(cls, cfg, key, value):
+        if key != "cheb_weights":
+            return super()._option(cfg, key, value)
+        w = [float(x) for x in value]
+        if len(w) > 16:
+            raise TypeError("at most 16 chebyshev weights")
+        cfg.cheb_weights = (C.c_double * 16)(*w)
 
-    def SetApproxMode(self, v):  # :387-395
-        self._set(self.P_APPROX, v)
-
-    def SetDrive(self, v):  # :398-406
-        self._set(self.P_DRIVE, v)
-
-    def SetOutputLevel(self, v):  # :420-429
-        self._set(self.P_OUTPUT_LEVEL, v)
-
-    def SetClipLevel(self, v):  # :432-441
-        self._set(self.P_CLIP_LEVEL, v)
-
-    def SetShape(self, v):  # :444-452
-        self._set(self.P_SHAPE, v)
-
-    def SetBias(self, v):  # :455-463
-        self._set(self.P_BIAS, v)
-
-    def SetChebyshevOrder(self, v):  # :466-474
-        self._set(self.P_CHEB_ORDER, v)
-
-    def SetChebyshevHarmonicMode(self, v):  # :477-485
-        self._set(self.P_CHEB_HARMONIC, v)
+    SetMode = _setter(P_MODE)  # :376-384
+    SetApproxMode = _setter(P_APPROX)  # :387-395
+    SetDrive = _setter(P_DRIVE)  # :398-406
+    SetOutputLevel = _setter(P_OUTPUT_LEVEL)  # :420-429
+    SetClipLevel = _setter(P_CLIP_LEVEL)  # :432-441
+    SetShape = _setter(P_SHAPE)  # :444-452
+    SetBias = _setter(P_BIAS)  # :455-463
+    SetChebyshevOrder = _setter(P_CHEB_ORDER)  # :466-474
+    SetChebyshevHarmonicMode = _setter(P_CHEB_HARMONIC)  # :477-485
+    SetChebyshevGainLevel = _setter(P_CHEB_GAIN)  # :493-502
+    Mode = _getter("mode")  # :567-588
+    Drive = _getter("drive")
+    OutputLevel = _getter("output_level")
+    ClipLevel = _getter("clip_level")
+    Shape = _getter("shape")
+    Bias = _getter("bias")
+    ChebyshevOrder = _getter("cheb_order")
 
     def SetChebyshevInvert(self, on: bool):  # :488-490
         self._set(self.P_CHEB_INVERT, 1 if on else 0)
-
-    def SetChebyshevGainLevel(self, v):  # :493-502
-        self._set(self.P_CHEB_GAIN, v)
 
     def SetChebyshevDCBypass(self, on: bool):  # :505-507
         self._set(self.P_CHEB_DC_BYPASS, 1 if on else 0)
@@ -886,42 +683,16 @@ class Distortion(_ShaperHandle):
         w = f64(weights).reshape(-1)
         check(lib().ad_distortion_set_weights(self._h, ptr(w), int(w.size)))
 
-    def Mode(self) -> int:  # :567-588
-        return self.config().mode
-
-    def Drive(self) -> float:
-        return self.config().drive
-
-    def OutputLevel(self) -> float:
-        return self.config().output_level
-
-    def ClipLevel(self) -> float:
-        return self.config().clip_level
-
-    def Shape(self) -> float:
-        return self.config().shape
-
-    def Bias(self) -> float:
-        return self.config().bias
-
-    def ChebyshevOrder(self) -> int:
-        return self.config().cheb_order
-
     def derived(self):
         """dict(atan_scale=atan(1 + 4 shape), scale6=1 + 6 shape, scale2=1 + 2 shape, one_minus_mix,
         weights_active) of ad_distortion_derived: the constants the host computes for the kernels."""
-        v = [C.c_double() for _ in range(4)]
-        w = C.c_int()
-        check(lib().ad_distortion_derived(self._h, *[C.byref(x) for x in v], C.byref(w)))
-        return dict(atan_scale=v[0].value, scale6=v[1].value, scale2=v[2].value, one_minus_mix=v[3].value,
-                    weights_active=bool(w.value))
+        *v, w = self._out("derived", _F64 * 4 + _INT)
+        return dict(atan_scale=v[0], scale6=v[1], scale2=v[2], one_minus_mix=v[3], weights_active=bool(w))
 
     def kernel_info(self):
         """(samples of a row per pointwise workgroup; channels per workgroup, samples staged per chunk and
         lds_bytes of the DC-bypass kernel) of ad_distortion_kernel_info."""
-        v = [C.c_int() for _ in range(4)]
-        check(lib().ad_distortion_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._out("kernel_info", _INT * 4)
 
     def curve(self, x):
         """shapeSample(x) * outputLevel with the finite check, by the device
@@ -940,111 +711,52 @@ class BitCrusher(_ShaperHandle):
 
     P_SAMPLE_RATE, P_BIT_DEPTH, P_MIX, P_DOWNSAMPLE = range(4)  # AD_BITCRUSHER_*
     _kind = "bitcrusher"
+    _name = "bitcrusher"
     _config = BitCrusherConfig
     _options = ("bit_depth", "mix")
     _int_options = ("downsample",)
 
-    def SetBitDepth(self, v):  # :149-160
-        self._set(self.P_BIT_DEPTH, v)
-
-    def SetDownsample(self, v):  # :163-172
-        self._set(self.P_DOWNSAMPLE, v)
-
-    def BitDepth(self) -> float:  # :214-220
-        return self.config().bit_depth
-
-    def Downsample(self) -> int:
-        return self.config().downsample
+    SetBitDepth = _setter(P_BIT_DEPTH)  # :149-160
+    SetDownsample = _setter(P_DOWNSAMPLE)  # :163-172
+    BitDepth = _getter("bit_depth")  # :214-220
+    Downsample = _getter("downsample")
 
     def derived(self, channel: int = 0):
         """dict(quant_levels, counter, hold_value) of ad_bitcrusher_derived: quantLevels = exp2(bitDepth - 1)
         as the host computed it, holdCounter, and holdValue of `channel`."""
-        q, c, h = C.c_double(), C.c_int(), C.c_double()
-        check(lib().ad_bitcrusher_derived(self._h, int(channel), C.byref(q), C.byref(c), C.byref(h)))
-        return dict(quant_levels=q.value, counter=c.value, hold_value=h.value)
+        q, c, h = self._out("derived", _F64 + _INT + _F64, int(channel))
+        return dict(quant_levels=q, counter=c, hold_value=h)
 
     def kernel_info(self):
         """(samples of a row per workgroup, the staged span of whole hold periods, lds_bytes) of
         ad_bitcrusher_kernel_info."""
-        v = [C.c_int() for _ in range(3)]
-        check(lib().ad_bitcrusher_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._out("kernel_info", _INT * 3)
 
 
-class _DynHandle(_Handle):
-    """What TransientShaper and DeEsser share: a config structure, options as
-    keywords, set_param with the int parameters as whole numbers, and the
-    host-only derived values of a config."""
+class _DynHandle(_ConfigHandle):
+    """What TransientShaper and DeEsser share: the attack and release times
+    and their coefficients."""
 
-    _config = None
-    _options = ()
-    _int_options = ()
-
-    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
-        cfg = self._config()
-        if config is None:
-            self._fn("default_config")(C.byref(cfg), float(sample_rate))
-        else:
-            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        for k, v in options.items():
-            if k in self._int_options:
-                setattr(cfg, k, int(v))
-            elif k in self._options:
-                setattr(cfg, k, float(v))
-            else:
-                raise TypeError(f"unknown {self._kind} option {k!r}")
-        check(self._fn("create")(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
-
-    def _set(self, which: int, v):
-        check(self._fn("set_param")(self._h, which, float(v)))
-
-    def config(self):
-        cfg = self._config()
-        check(self._fn("get_config")(self._h, C.byref(cfg)))
-        return cfg
-
-    def SetSampleRate(self, v):
-        self._set(0, v)
-
-    def SetAttack(self, v):
-        self._set(self.P_ATTACK, v)
-
-    def SetRelease(self, v):
-        self._set(self.P_RELEASE, v)
-
-    def SetAttackCoeff(self, v):  # attackCoeff, for a caller whose exp is not the C library's
-        self._set(self.P_ATTACK_COEFF, v)
-
-    def SetReleaseCoeff(self, v):
-        self._set(self.P_RELEASE_COEFF, v)
-
-    def SampleRate(self) -> float:
-        return self.config().sample_rate
-
-    def Attack(self) -> float:
-        return self.config().attack_ms
-
-    def Release(self) -> float:
-        return self.config().release_ms
+    SetAttack = _setter("P_ATTACK")
+    SetRelease = _setter("P_RELEASE")
+    SetAttackCoeff = _setter("P_ATTACK_COEFF")  # attackCoeff, for a caller whose exp is not the C library's
+    SetReleaseCoeff = _setter("P_RELEASE_COEFF")
+    Attack = _getter("attack_ms")
+    Release = _getter("release_ms")
 
 
 def transient_derived(cfg: TransientConfig):
     """(attack_coeff, release_coeff) in use for a config, of ad_transient_derived: host only."""
-    a, r = C.c_double(), C.c_double()
-    check(lib().ad_transient_derived(C.byref(cfg), C.byref(a), C.byref(r)))
-    return a.value, r.value
+    return _outputs(lib().ad_transient_derived, _F64 * 2, C.byref(cfg))
 
 
 def deesser_derived(cfg: DeEsserConfig) -> dict:
     """dict(section=(b0, b1, b2, a1, a2), band_norm, threshold_log2, knee_width_log2, range_lin, attack_coeff,
     release_coeff) for a config, of ad_deesser_derived: what the reference caches, host only."""
     sec = (C.c_double * 5)()
-    v = [C.c_double() for _ in range(6)]
-    check(lib().ad_deesser_derived(C.byref(cfg), sec, *[C.byref(x) for x in v]))
-    return dict(section=tuple(sec), band_norm=v[0].value, threshold_log2=v[1].value, knee_width_log2=v[2].value,
-                range_lin=v[3].value, attack_coeff=v[4].value, release_coeff=v[5].value)
+    v = _outputs(lib().ad_deesser_derived, _F64 * 6, C.byref(cfg), sec)
+    return dict(section=tuple(sec), band_norm=v[0], threshold_log2=v[1], knee_width_log2=v[2], range_lin=v[3],
+                attack_coeff=v[4], release_coeff=v[5])
 
 
 class TransientShaper(_DynHandle):
@@ -1058,35 +770,25 @@ class TransientShaper(_DynHandle):
     (P_SAMPLE_RATE, P_ATTACK_AMOUNT, P_SUSTAIN_AMOUNT, P_ATTACK, P_RELEASE, P_ATTACK_COEFF,
      P_RELEASE_COEFF) = range(7)  # AD_TRANSIENT_*
     _kind = "transient"
+    _name = "transient"
     _config = TransientConfig
     _options = ("attack_amount", "sustain_amount", "attack_ms", "release_ms", "attack_coeff", "release_coeff")
 
-    def SetAttackAmount(self, v):  # :57-66
-        self._set(self.P_ATTACK_AMOUNT, v)
-
-    def SetSustainAmount(self, v):  # :69-78
-        self._set(self.P_SUSTAIN_AMOUNT, v)
-
-    def AttackAmount(self) -> float:  # :120-132
-        return self.config().attack_amount
-
-    def SustainAmount(self) -> float:
-        return self.config().sustain_amount
+    SetAttackAmount = _setter(P_ATTACK_AMOUNT)  # :57-66
+    SetSustainAmount = _setter(P_SUSTAIN_AMOUNT)  # :69-78
+    AttackAmount = _getter("attack_amount")  # :120-132
+    SustainAmount = _getter("sustain_amount")
 
     def derived(self):
         return transient_derived(self.config())
 
     def kernel_info(self):
         """(channels per workgroup, samples staged per chunk, lds_bytes) of the walk, of ad_transient_kernel_info."""
-        v = [C.c_int() for _ in range(3)]
-        check(lib().ad_transient_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._out("kernel_info", _INT * 3)
 
     def get_state(self, channel: int = 0) -> float:
         """The envelope of `channel`."""
-        e = C.c_double()
-        check(lib().ad_transient_get_state(self._h, int(channel), C.byref(e)))
-        return e.value
+        return self._out("get_state", _F64, int(channel))[0]
 
     def set_state(self, channel: int, envelope: float):
         check(lib().ad_transient_set_state(self._h, int(channel), float(envelope)))
@@ -1105,75 +807,37 @@ class DeEsser(_DynHandle):
     SPLIT_BAND, WIDEBAND = 0, 1  # DeEsserMode :15-25
     DETECT_BANDPASS, DETECT_HIGHPASS = 0, 1  # DeEsserDetector :30-39
     _kind = "deesser"
+    _name = "deesser"
     _config = DeEsserConfig
     _options = ("freq_hz", "q", "threshold_db", "ratio", "knee_db", "attack_ms", "release_ms", "range_db",
                 "attack_coeff", "release_coeff")
     _int_options = ("mode", "detector", "listen", "filter_order")
 
-    def SetFrequency(self, v):  # :228-244
-        self._set(self.P_FREQ, v)
-
-    def SetQ(self, v):  # :248-259
-        self._set(self.P_Q, v)
-
-    def SetThreshold(self, v):  # :263-272
-        self._set(self.P_THRESHOLD, v)
-
-    def SetRatio(self, v):  # :276-287
-        self._set(self.P_RATIO, v)
-
-    def SetKnee(self, v):  # :291-302
-        self._set(self.P_KNEE, v)
-
-    def SetRange(self, v):  # :336-347
-        self._set(self.P_RANGE, v)
-
-    def SetMode(self, v):  # :350-358
-        self._set(self.P_MODE, v)
-
-    def SetDetector(self, v):  # :361-370
-        self._set(self.P_DETECTOR, v)
+    SetFrequency = _setter(P_FREQ)  # :228-244
+    SetQ = _setter(P_Q)  # :248-259
+    SetThreshold = _setter(P_THRESHOLD)  # :263-272
+    SetRatio = _setter(P_RATIO)  # :276-287
+    SetKnee = _setter(P_KNEE)  # :291-302
+    SetRange = _setter(P_RANGE)  # :336-347
+    SetMode = _setter(P_MODE)  # :350-358
+    SetDetector = _setter(P_DETECTOR)  # :361-370
+    SetFilterOrder = _setter(P_FILTER_ORDER)  # :381-391
+    Frequency = _getter("freq_hz")  # :186-222
+    Q = _getter("q")
+    Threshold = _getter("threshold_db")
+    Ratio = _getter("ratio")
+    Knee = _getter("knee_db")
+    Range = _getter("range_db")
+    Mode = _getter("mode")
+    Detector = _getter("detector")
+    Listen = _getter("listen", bool)
+    FilterOrder = _getter("filter_order")
 
     def SetListen(self, on: bool):  # :375-377
         self._set(self.P_LISTEN, 1 if on else 0)
 
-    def SetFilterOrder(self, v):  # :381-391
-        self._set(self.P_FILTER_ORDER, v)
-
-    def Frequency(self) -> float:  # :186-222
-        return self.config().freq_hz
-
-    def Q(self) -> float:
-        return self.config().q
-
-    def Threshold(self) -> float:
-        return self.config().threshold_db
-
-    def Ratio(self) -> float:
-        return self.config().ratio
-
-    def Knee(self) -> float:
-        return self.config().knee_db
-
-    def Range(self) -> float:
-        return self.config().range_db
-
-    def Mode(self) -> int:
-        return self.config().mode
-
-    def Detector(self) -> int:
-        return self.config().detector
-
-    def Listen(self) -> bool:
-        return bool(self.config().listen)
-
-    def FilterOrder(self) -> int:
-        return self.config().filter_order
-
     def GetMetrics(self, channel: int = 0):  # :499-501 -> (DetectionLevel, GainReduction)
-        d, g = C.c_double(), C.c_double()
-        check(lib().ad_deesser_metrics(self._h, int(channel), C.byref(d), C.byref(g)))
-        return d.value, g.value
+        return self._out("metrics", _F64 * 2, int(channel))
 
     def ResetMetrics(self):  # :504-506
         check(lib().ad_deesser_reset_metrics(self._h))
@@ -1184,9 +848,7 @@ class DeEsser(_DynHandle):
     def kernel_info(self):
         """(channels per workgroup, samples staged per chunk, lds_bytes, cascades walked) of the walk the next
         call runs, of ad_deesser_kernel_info."""
-        v = [C.c_int() for _ in range(4)]
-        check(lib().ad_deesser_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._out("kernel_info", _INT * 4)
 
     def get_state(self, channel: int = 0):
         """(envelope, detect [4][2], band [4][2]) of `channel`: {d0, d1} of each section."""
@@ -1234,7 +896,7 @@ def vocoder_derived(cfg: VocoderConfig) -> dict:
                 ds_attack=np.array(t.ds_attack[:nb if on else 0]), ds_release=np.array(t.ds_release[:nb if on else 0]))
 
 
-class Vocoder(_Handle):
+class Vocoder(_ConfigHandle):
     """effects.Vocoder (vocoder.go:199-833) for `channels` instances sharing one
     configuration: NewVocoder(sample_rate, options...) with the options as
     keywords (layout, synth_q, attack_ms, release_ms, input_level, synth_level,
@@ -1247,89 +909,39 @@ class Vocoder(_Handle):
      P_DOWNSAMPLING) = range(8)  # AD_VOCODER_*
     THIRD_OCTAVE, BARK = 0, 1  # BandLayout :15-25
     _kind = "vocoder"
+    _name = "vocoder"
+    _config = VocoderConfig
     _options = ("synth_q", "attack_ms", "release_ms", "input_level", "synth_level", "vocoder_level")
+    _int_options = ("layout",)
+    _bool_options = ("downsample",)
 
-    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
-        cfg = VocoderConfig()
-        if config is None:
-            lib().ad_vocoder_default_config(C.byref(cfg), float(sample_rate))
-        else:
-            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        for k, v in options.items():
-            if k == "layout":
-                cfg.layout = int(v)
-            elif k == "downsample":
-                cfg.downsample = 1 if v else 0
-            elif k in self._options:
-                setattr(cfg, k, float(v))
-                if k == "synth_q":
-                    cfg.synth_q_set = 1
-            else:
-                raise TypeError(f"unknown vocoder option {k!r}")
-        check(lib().ad_vocoder_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+    @classmethod
+    def _option(cls, cfg, key, value):
+        super()._option(cfg, key, value)
+        if key == "synth_q":
+            cfg.synth_q_set = 1
 
-    def _set(self, which: int, v):
-        check(lib().ad_vocoder_set_param(self._h, which, float(v)))
-
-    def config(self) -> VocoderConfig:
-        cfg = VocoderConfig()
-        check(lib().ad_vocoder_get_config(self._h, C.byref(cfg)))
-        return cfg
-
-    def SetSampleRate(self, v):  # :673-683
-        self._set(self.P_SAMPLE_RATE, v)
-
-    def SetAttack(self, v):  # :772-783
-        self._set(self.P_ATTACK, v)
-
-    def SetRelease(self, v):  # :786-797
-        self._set(self.P_RELEASE, v)
-
-    def SetInputLevel(self, v):  # :800-809
-        self._set(self.P_INPUT_LEVEL, v)
-
-    def SetSynthLevel(self, v):  # :812-821
-        self._set(self.P_SYNTH_LEVEL, v)
-
-    def SetVocoderLevel(self, v):  # :824-833
-        self._set(self.P_VOCODER_LEVEL, v)
+    SetSampleRate = _setter(P_SAMPLE_RATE)  # :673-683
+    SetAttack = _setter(P_ATTACK)  # :772-783
+    SetRelease = _setter(P_RELEASE)  # :786-797
+    SetInputLevel = _setter(P_INPUT_LEVEL)  # :800-809
+    SetSynthLevel = _setter(P_SYNTH_LEVEL)  # :812-821
+    SetVocoderLevel = _setter(P_VOCODER_LEVEL)  # :824-833
+    SampleRate = _getter("sample_rate")  # :688-717
+    Layout = _getter("layout")
+    SynthesisQ = _getter("synth_q")
+    Attack = _getter("attack_ms")
+    Release = _getter("release_ms")
+    InputLevel = _getter("input_level")
+    SynthLevel = _getter("synth_level")
+    VocoderLevel = _getter("vocoder_level")
+    Downsampling = _getter("downsample", bool)
 
     def SetDownsampling(self, on: bool):  # :737-769
         self._set(self.P_DOWNSAMPLING, 1 if on else 0)
 
-    def SampleRate(self) -> float:  # :688-717
-        return self.config().sample_rate
-
-    def Layout(self) -> int:
-        return self.config().layout
-
     def NumBands(self) -> int:
-        n = C.c_int()
-        check(lib().ad_vocoder_num_bands(self._h, C.byref(n)))
-        return n.value
-
-    def SynthesisQ(self) -> float:
-        return self.config().synth_q
-
-    def Attack(self) -> float:
-        return self.config().attack_ms
-
-    def Release(self) -> float:
-        return self.config().release_ms
-
-    def InputLevel(self) -> float:
-        return self.config().input_level
-
-    def SynthLevel(self) -> float:
-        return self.config().synth_level
-
-    def VocoderLevel(self) -> float:
-        return self.config().vocoder_level
-
-    def Downsampling(self) -> bool:
-        return bool(self.config().downsample)
+        return self._out("num_bands", _INT)[0]
 
     def DownsampleFactors(self):  # :722-731: None with downsampling off
         f, n = (C.c_int * 32)(), C.c_int()
@@ -1341,16 +953,13 @@ class Vocoder(_Handle):
 
     def kernel_info(self):
         """(lanes per channel, samples per chunk, lds_bytes of a workgroup) of ad_vocoder_kernel_info."""
-        v = [C.c_int() for _ in range(3)]
-        check(lib().ad_vocoder_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._out("kernel_info", _INT * 3)
 
     def get_state(self, channel: int = 0):
         """(state [9][32], downsampleCount) of `channel`: rows {analysis s0, s1, synthesis s0, s1, decimated s0,
         s1, envelope} by band, then the anti-alias {s0, s1} by group."""
-        st, cnt = np.zeros((9, 32)), C.c_int()
-        check(lib().ad_vocoder_get_state(self._h, int(channel), ptr(st), C.byref(cnt)))
-        return st, cnt.value
+        st = np.zeros((9, 32))
+        return (st,) + self._out("get_state", _INT, int(channel), ptr(st))
 
     def ProcessBlock(self, modulator, carrier) -> np.ndarray:  # :634-645 on host rows [channels][n]
         m = _as2d(np.ascontiguousarray(modulator, dtype=np.float64), self.channels)
@@ -1377,20 +986,18 @@ class Vocoder(_Handle):
 
     def process_device(self, d_mod: int, mod_stride: int, d_car: int, car_stride: int, d_out: int, out_stride: int,
                        n: int, stream: int | None = None):
-        check(lib().ad_vocoder_process_device(self._h, C.c_void_p(d_mod), int(mod_stride), C.c_void_p(d_car),
-                                              int(car_stride), C.c_void_p(d_out), int(out_stride), int(n),
-                                              C.c_void_p(stream or 0)))
+        check(self._device_fn(self._h, C.c_void_p(d_mod), int(mod_stride), C.c_void_p(d_car), int(car_stride),
+                              C.c_void_p(d_out), int(out_stride), int(n), C.c_void_p(stream or 0)))
 
 
 def lookahead_derived(cfg: LookaheadConfig) -> dict:
     """dict(attack_coeff, release_coeff, threshold_log2, delay_samples) for a config, of ad_lookahead_derived:
     what the limiter's Compressor core caches and the delay D, host only."""
-    a, r, th, d = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
-    check(lib().ad_lookahead_derived(C.byref(cfg), C.byref(a), C.byref(r), C.byref(th), C.byref(d)))
-    return dict(attack_coeff=a.value, release_coeff=r.value, threshold_log2=th.value, delay_samples=d.value)
+    a, r, th, d = _outputs(lib().ad_lookahead_derived, _F64 * 3 + _I64, C.byref(cfg))
+    return dict(attack_coeff=a, release_coeff=r, threshold_log2=th, delay_samples=d)
 
 
-class LookaheadLimiter(_Handle):
+class LookaheadLimiter(_ConfigHandle):
     """dynamics.LookaheadLimiter (lookahead_limiter.go:23-239) for `channels`
     instances sharing one configuration: NewLookaheadLimiter(sample_rate) with
     options as keywords (threshold_db, release_ms, lookahead_ms), or `config`
@@ -1399,53 +1006,18 @@ class LookaheadLimiter(_Handle):
 
     P_SAMPLE_RATE, P_THRESHOLD, P_RELEASE, P_LOOKAHEAD = range(4)  # AD_LOOKAHEAD_*
     _kind = "lookahead"
+    _name = "lookahead limiter"
+    _config = LookaheadConfig
     _options = ("threshold_db", "release_ms", "lookahead_ms")
 
-    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, config=None, **options):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
-        cfg = LookaheadConfig()
-        if config is None:
-            lib().ad_lookahead_default_config(C.byref(cfg), float(sample_rate))
-        else:
-            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(cfg))
-        for k, v in options.items():
-            if k not in self._options:
-                raise TypeError(f"unknown lookahead limiter option {k!r}")
-            setattr(cfg, k, float(v))
-        check(lib().ad_lookahead_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
-
-    def _set(self, which: int, v):
-        check(lib().ad_lookahead_set_param(self._h, which, float(v)))
-
-    def config(self) -> LookaheadConfig:
-        cfg = LookaheadConfig()
-        check(lib().ad_lookahead_get_config(self._h, C.byref(cfg)))
-        return cfg
-
-    def SetSampleRate(self, v):  # :146-161
-        self._set(self.P_SAMPLE_RATE, v)
-
-    def SetThreshold(self, v):  # :99-113
-        self._set(self.P_THRESHOLD, v)
-
-    def SetRelease(self, v):  # :116-130
-        self._set(self.P_RELEASE, v)
-
-    def SetLookahead(self, v):  # :133-143
-        self._set(self.P_LOOKAHEAD, v)
-
-    def SampleRate(self) -> float:  # :164-173
-        return self.config().sample_rate
-
-    def Threshold(self) -> float:
-        return self.config().threshold_db
-
-    def Release(self) -> float:
-        return self.config().release_ms
-
-    def Lookahead(self) -> float:
-        return self.config().lookahead_ms
+    SetSampleRate = _setter(P_SAMPLE_RATE)  # :146-161
+    SetThreshold = _setter(P_THRESHOLD)  # :99-113
+    SetRelease = _setter(P_RELEASE)  # :116-130
+    SetLookahead = _setter(P_LOOKAHEAD)  # :133-143
+    SampleRate = _getter("sample_rate")  # :164-173
+    Threshold = _getter("threshold_db")
+    Release = _getter("release_ms")
+    Lookahead = _getter("lookahead_ms")
 
     def derived(self) -> dict:
         return lookahead_derived(self.config())
@@ -1455,9 +1027,7 @@ class LookaheadLimiter(_Handle):
 
     def get_state(self, channel: int = 0) -> float:
         """The detector envelope of `channel`."""
-        e = C.c_double()
-        check(lib().ad_lookahead_get_state(self._h, int(channel), C.byref(e)))
-        return e.value
+        return self._out("get_state", _F64, int(channel))[0]
 
     def gain(self, levels):
         """GainForLevel(level) by the device code a call runs.  Nothing advances."""
@@ -1496,8 +1066,8 @@ class LookaheadLimiter(_Handle):
 
     def process_device(self, d_buf: int, stride: int, n: int, stream: int | None = None, d_side: int = 0,
                        side_stride: int = 0, side_n: int = 0):
-        check(lib().ad_lookahead_process_device(self._h, C.c_void_p(d_buf), int(stride), C.c_void_p(d_side or None),
-                                                int(side_stride), int(side_n), int(n), C.c_void_p(stream or 0)))
+        check(self._device_fn(self._h, C.c_void_p(d_buf), int(stride), C.c_void_p(d_side or None), int(side_stride),
+                              int(side_n), int(n), C.c_void_p(stream or 0)))
 
 
 def _freq_args(freqs):
@@ -1523,11 +1093,8 @@ class MultiBandCrossover(_Handle):
     _kind = "xover"
 
     def __init__(self, freqs, order: int, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
         f, fp, nf = _freq_args(freqs)
-        check(lib().ad_xover_create(fp, nf, int(order), float(sample_rate), self.channels, int(device),
-                                    C.byref(self._h)))
+        self._create(channels, device, fp, nf, int(order), float(sample_rate))
         self._freqs, self._order, self._fs = f.copy(), int(order), float(sample_rate)
         self._sections = crossover_sections(f, order, sample_rate)
 
@@ -1549,8 +1116,8 @@ class MultiBandCrossover(_Handle):
 
     def process_device(self, d_in: int, in_stride: int, d_bands: int, row_stride: int, band_stride: int, n: int,
                        stream: int | None = None):
-        check(lib().ad_xover_process_device(self._h, C.c_void_p(d_in), int(in_stride), C.c_void_p(d_bands),
-                                            int(row_stride), int(band_stride), int(n), C.c_void_p(stream or 0)))
+        check(self._device_fn(self._h, C.c_void_p(d_in), int(in_stride), C.c_void_p(d_bands), int(row_stride),
+                              int(band_stride), int(n), C.c_void_p(stream or 0)))
 
     def get_state(self, channel: int = 0) -> np.ndarray:
         """[stages][2][S][2] {s0, s1} of `channel`."""
@@ -1564,9 +1131,7 @@ class MultiBandCrossover(_Handle):
 
     def kernel_info(self):
         """(waves per workgroup, samples per tile, lds_bytes) of ad_xover_kernel_info."""
-        v = [C.c_int() for _ in range(3)]
-        check(lib().ad_xover_kernel_info(self._h, *[C.byref(x) for x in v]))
-        return tuple(x.value for x in v)
+        return self._out("kernel_info", _INT * 3)
 
     def set_pipelined(self, on: bool):
         """All stages in one launch as a pipeline over time tiles (True, the default), or one stage per launch;
@@ -1612,19 +1177,17 @@ class MultibandCompressor(_Handle):
     """dynamics.MultibandCompressor (dsp/effects/dynamics/multiband.go) on `channels` lanes: the crossover, one
     compressor per band, the bands summed in band order.  `configs`: one BandConfig-like dict per band
     (NewMultibandCompressorWithConfig :130-150); a key left out, None, or 0 for Ratio / AttackMs / ReleaseMs
-    keeps the default."""
+    keeps the default.  Its per-band setters are SetBand<name>(band, v) for every name of _DYNAMICS_SETTERS,
+    with SetAllBands<name>(v) where the reference has one."""
 
     _kind = "multiband"
 
     def __init__(self, freqs, order: int, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE,
                  configs=None):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
         f, fp, nf = _freq_args(freqs)
         if configs is not None and len(configs) != nf + 1:  # :131-135
             raise ErrInvalidArgument(AD_ERR_INVALID_ARGUMENT, f"expected {nf + 1} band configs, got {len(configs)}")
-        check(lib().ad_multiband_create(fp, nf, int(order), float(sample_rate), self.channels, int(device),
-                                        C.byref(self._h)))
+        self._create(channels, device, fp, nf, int(order), float(sample_rate))
         self._freqs, self._order, self._fs = f.copy(), int(order), float(sample_rate)
         for i, cfg in enumerate(configs or ()):
             self.SetBandConfig(i, cfg)
@@ -1655,46 +1218,6 @@ class MultibandCompressor(_Handle):
             setattr(cfg, k, v)
         check(lib().ad_multiband_set_band(self._h, int(band), C.byref(cfg)))  # rejected: nothing changes
 
-    # per-band setters :190-329
-    def SetBandThreshold(self, band, db):
-        self._set(band, threshold_db=float(db))
-
-    def SetBandRatio(self, band, ratio):
-        self._set(band, ratio=float(ratio))
-
-    def SetBandKnee(self, band, db):
-        self._set(band, knee_db=float(db))
-
-    def SetBandAttack(self, band, ms):
-        self._set(band, attack_ms=float(ms))
-
-    def SetBandRelease(self, band, ms):
-        self._set(band, release_ms=float(ms))
-
-    def SetBandMakeupGain(self, band, db):  # :242-249: turns auto makeup off
-        self._set(band, makeup_db=float(db), auto_makeup=0)
-
-    def SetBandAutoMakeup(self, band, on):
-        self._set(band, auto_makeup=int(bool(on)))
-
-    def SetBandTopology(self, band, topology):
-        self._set(band, topology=int(topology))
-
-    def SetBandDetectorMode(self, band, mode):
-        self._set(band, detector_mode=int(mode))
-
-    def SetBandFeedbackRatioScale(self, band, on):
-        self._set(band, feedback_ratio_scale=int(bool(on)))
-
-    def SetBandRMSWindow(self, band, ms):
-        self._set(band, rms_window_ms=float(ms))
-
-    def SetBandSidechainLowCut(self, band, hz):
-        self._set(band, sidechain_low_cut_hz=float(hz))
-
-    def SetBandSidechainHighCut(self, band, hz):
-        self._set(band, sidechain_high_cut_hz=float(hz))
-
     def SetBandConfig(self, band, cfg):  # :322-329, applyBandConfig :563-658: stops at the first rejected field
         self._band(band)
         unknown = set(cfg) - {k for k, _, _ in _BAND_CONFIG}
@@ -1710,32 +1233,8 @@ class MultibandCompressor(_Handle):
         for b in range(self.NumBands()):
             getattr(self, setter)(b, v)
 
-    def SetAllBandsThreshold(self, db):
-        self._all("SetBandThreshold", db)
-
-    def SetAllBandsRatio(self, ratio):
-        self._all("SetBandRatio", ratio)
-
-    def SetAllBandsKnee(self, db):
-        self._all("SetBandKnee", db)
-
-    def SetAllBandsAttack(self, ms):
-        self._all("SetBandAttack", ms)
-
-    def SetAllBandsRelease(self, ms):
-        self._all("SetBandRelease", ms)
-
-    def SetAllBandsTopology(self, topology):
-        self._all("SetBandTopology", topology)
-
-    def SetAllBandsDetectorMode(self, mode):
-        self._all("SetBandDetectorMode", mode)
-
-    def SetAllBandsFeedbackRatioScale(self, on):
-        self._all("SetBandFeedbackRatioScale", on)
-
-    def SetAllBandsRMSWindow(self, ms):
-        self._all("SetBandRMSWindow", ms)
+    def ProcessInPlace(self, buf):  # :476-490
+        self._process(buf)
 
     def ProcessInPlaceMulti(self, x) -> np.ndarray:  # :507-523 -> [bands][channels][n]; x is not written
         b = _as2d(np.ascontiguousarray(x, dtype=np.float64), self.channels)
@@ -1759,12 +1258,7 @@ class MultibandCompressor(_Handle):
                                                       C.c_void_p(stream or 0)))
 
     def GetMetrics(self, channel: int = 0) -> list:  # :537-544 -> per band (InputPeak, OutputPeak, GainReduction)
-        out = []
-        for b in range(self.NumBands()):
-            v = [C.c_double() for _ in range(3)]
-            check(lib().ad_multiband_metrics(self._h, b, int(channel), *[C.byref(x) for x in v]))
-            out.append(tuple(x.value for x in v))
-        return out
+        return [self._out("metrics", _F64 * 3, b, int(channel)) for b in range(self.NumBands())]
 
     def ResetMetrics(self):  # :547-551
         check(lib().ad_multiband_reset_metrics(self._h))
@@ -1779,6 +1273,25 @@ class MultibandCompressor(_Handle):
     def SetChunk(self, samples: int):
         """Runs every call in passes of at most `samples` samples (0: as many as the scratch cap allows)."""
         check(lib().ad_multiband_set_chunk(self._h, int(samples)))
+
+
+def _band_setter(field, kind, also):
+    def set_(self, band, v):
+        self._set(band, **{field: kind(v)}, **also)
+    return set_
+
+
+def _all_bands_setter(setter):
+    def set_(self, v):
+        self._all(setter, v)
+    return set_
+
+
+for _name, _field, _kind, _also, _all_bands in _DYNAMICS_SETTERS:
+    setattr(MultibandCompressor, "SetBand" + _name, _band_setter(_field, _kind, _also))
+    if _all_bands:
+        setattr(MultibandCompressor, "SetAllBands" + _name, _all_bands_setter("SetBand" + _name))
+del _name, _field, _kind, _also, _all_bands
 
 
 # window.Type (dsp/window/window.go:12-16) of the windows the STFT processors take
@@ -1807,22 +1320,20 @@ def spectral_window(window_type: int, n: int) -> np.ndarray:
     return s
 
 
-class _StftHandle(_Handle):
+class _StftHandle(_ConfigHandle):
     """What SpectralFreeze and SpectralPitchShifter share: the frame size and
-    the window, whose table this layer computes, and the Process forms."""
+    the window, whose table this layer computes, and the Process forms.  The
+    constructors take no `config`: a config's window table is this layer's."""
 
-    _config = None
+    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, **options):
+        super().__init__(sample_rate, channels, device, None, **options)
 
-    def _set(self, which: int, v):
-        check(self._fn("set_param")(self._h, which, float(v)))
-
-    def config(self):
-        cfg = self._config()
-        check(self._fn("get_config")(self._h, C.byref(cfg)))
+    @classmethod
+    def _make_config(cls, sample_rate, config=None, **options):
+        cfg = super()._make_config(sample_rate, config, **options)
+        cfg._window = spectral_window(cfg.window_type, max(cfg.frame_size, 0))  # the table lives with the structure
+        cfg.window = ptr(cfg._window)
         return cfg
-
-    def SetSampleRate(self, v):
-        self._set(0, v)
 
     def SetFrameSize(self, size: int):
         size = int(size)
@@ -1835,14 +1346,8 @@ class _StftHandle(_Handle):
         w = spectral_window(window_type, self.FrameSize())
         check(self._fn("set_window")(self._h, int(window_type), ptr(w)))
 
-    def SampleRate(self) -> float:
-        return self.config().sample_rate
-
-    def FrameSize(self) -> int:
-        return self.config().frame_size
-
-    def WindowType(self) -> int:
-        return self.config().window_type
+    FrameSize = _getter("frame_size")
+    WindowType = _getter("window_type")
 
     def Process(self, x) -> np.ndarray:
         out = f64(x).copy()
@@ -1870,32 +1375,18 @@ class SpectralFreeze(_StftHandle):
     PhaseHold, PhaseAdvance = 0, 1  # SpectralFreezePhaseMode :23-28
     P_SAMPLE_RATE, P_HOP, P_MIX, P_PHASE_MODE, P_FROZEN = range(5)  # AD_SPECFREEZE_*
     _kind = "specfreeze"
+    _name = "spectral freeze"
     _config = SpecFreezeConfig
+    _options = ("mix",)
+    _int_options = ("frame_size", "hop_size", "phase_mode", "frozen", "window_type")
 
-    def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, **options):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
-        cfg = SpecFreezeConfig()
-        lib().ad_specfreeze_default_config(C.byref(cfg), float(sample_rate))
-        for k, v in options.items():
-            if k in ("frame_size", "hop_size", "phase_mode", "frozen", "window_type"):
-                setattr(cfg, k, int(v))
-            elif k == "mix":
-                cfg.mix = float(v)
-            else:
-                raise TypeError(f"unknown spectral freeze option {k!r}")
-        w = spectral_window(cfg.window_type, max(cfg.frame_size, 0))
-        cfg.window = ptr(w)
-        check(lib().ad_specfreeze_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
-
-    def SetHopSize(self, hop: int):
-        self._set(self.P_HOP, hop)
-
-    def SetMix(self, mix: float):
-        self._set(self.P_MIX, mix)
-
-    def SetPhaseMode(self, mode: int):
-        self._set(self.P_PHASE_MODE, mode)
+    SetHopSize = _setter(P_HOP)
+    SetMix = _setter(P_MIX)
+    SetPhaseMode = _setter(P_PHASE_MODE)
+    HopSize = _getter("hop_size")
+    Mix = _getter("mix")
+    PhaseMode = _getter("phase_mode")
+    Frozen = _getter("frozen", bool)
 
     def SetFrozen(self, frozen: bool):
         self._set(self.P_FROZEN, 1 if frozen else 0)
@@ -1906,25 +1397,11 @@ class SpectralFreeze(_StftHandle):
     def Unfreeze(self):
         self.SetFrozen(False)
 
-    def HopSize(self) -> int:
-        return self.config().hop_size
-
-    def Mix(self) -> float:
-        return self.config().mix
-
-    def PhaseMode(self) -> int:
-        return self.config().phase_mode
-
-    def Frozen(self) -> bool:
-        return bool(self.config().frozen)
-
     def state(self):
         """(heldMagnitude [channels][N/2+1], phaseAcc [channels][N/2+1], hasFrozenFrame) of ad_specfreeze_state."""
         bins = self.FrameSize() // 2 + 1
         held, acc = np.zeros((self.channels, bins)), np.zeros((self.channels, bins))
-        has = C.c_int()
-        check(lib().ad_specfreeze_state(self._h, ptr(held), ptr(acc), C.byref(has)))
-        return held, acc, bool(has.value)
+        return held, acc, bool(self._out("state", _INT, ptr(held), ptr(acc))[0])
 
     def norm(self, n: int) -> np.ndarray:
         """The overlap-add norm (sum of w^2 in ascending frame order) of a call of n samples, by the device code."""
@@ -1954,23 +1431,13 @@ class SpectralPitchShifter(_StftHandle):
 
     P_SAMPLE_RATE, P_RATIO, P_HOP, P_RESAMPLE_QUALITY = range(4)  # AD_PITCHSPEC_*
     _kind = "pitchspec"
+    _name = "spectral pitch shifter"
     _config = PitchSpecConfig
+    _options = ("pitch_ratio",)
+    _int_options = ("frame_size", "analysis_hop", "window_type", "resample_quality")
 
     def __init__(self, sample_rate: float = 48000.0, channels: int = 1, device: int = DEVICE, **options):
-        self.channels = int(channels)
-        self._h = C.c_void_p()
-        cfg = PitchSpecConfig()
-        lib().ad_pitchspec_default_config(C.byref(cfg), float(sample_rate))
-        for k, v in options.items():
-            if k in ("frame_size", "analysis_hop", "window_type", "resample_quality"):
-                setattr(cfg, k, int(v))
-            elif k == "pitch_ratio":
-                cfg.pitch_ratio = float(v)
-            else:
-                raise TypeError(f"unknown spectral pitch shifter option {k!r}")
-        w = spectral_window(cfg.window_type, max(cfg.frame_size, 0))
-        cfg.window = ptr(w)
-        check(lib().ad_pitchspec_create(C.byref(cfg), self.channels, int(device), C.byref(self._h)))
+        super().__init__(sample_rate, channels, device, **options)
         self._sync_taps()
 
     def _sync_taps(self):
@@ -1988,8 +1455,12 @@ class SpectralPitchShifter(_StftHandle):
         super().SetFrameSize(size)
         self._sync_taps()
 
-    def SetPitchRatio(self, ratio: float):
-        self._set(self.P_RATIO, ratio)
+    SetPitchRatio = _setter(P_RATIO)
+    SetAnalysisHop = _setter(P_HOP)
+    SetResampleQuality = _setter(P_RESAMPLE_QUALITY)
+    PitchRatio = _getter("pitch_ratio")
+    AnalysisHop = _getter("analysis_hop")
+    ResampleQuality = _getter("resample_quality")
 
     def SetPitchSemitones(self, semitones: float):  # :164-177
         s = float(semitones)
@@ -1997,39 +1468,18 @@ class SpectralPitchShifter(_StftHandle):
             raise ErrInvalidArgument(AD_ERR_INVALID_ARGUMENT, f"spectral pitch shifter semitones must be finite: {s}")
         self.SetPitchRatio(2.0 ** (s / 12.0))
 
-    def SetAnalysisHop(self, hop: int):
-        self._set(self.P_HOP, hop)
-
-    def SetResampleQuality(self, q: int):
-        self._set(self.P_RESAMPLE_QUALITY, q)
-
-    def PitchRatio(self) -> float:
-        return self.config().pitch_ratio
-
     def PitchSemitones(self) -> float:  # :103
         return 12.0 * float(np.log2(self.PitchRatio()))
 
-    def AnalysisHop(self) -> int:
-        return self.config().analysis_hop
-
-    def ResampleQuality(self) -> int:
-        return self.config().resample_quality
-
     def EffectivePitchRatio(self) -> float:
-        r = C.c_double()
-        check(lib().ad_pitchspec_effective_ratio(self._h, C.byref(r)))
-        return r.value
+        return self._out("effective_ratio", _F64)[0]
 
     def SynthesisHop(self) -> int:
-        h = C.c_int()
-        check(lib().ad_pitchspec_synthesis_hop(self._h, C.byref(h)))
-        return h.value
+        return self._out("synthesis_hop", _INT)[0]
 
     def path(self) -> int:
         """0: the identity shortcut, 1: bin shifting, 2: time stretch (ad_pitchspec_path)."""
-        v = C.c_int()
-        check(lib().ad_pitchspec_path(self._h, C.byref(v)))
-        return v.value
+        return self._out("path", _INT)[0]
 
 
 class EffectChain(_FxChain):
@@ -2060,15 +1510,14 @@ class EffectChain(_FxChain):
         self._process(buf)
 
 
-class Filter:
+class Filter(_Handle):
     """fir.Filter (filter.go:11-172) for `channels` lanes sharing the taps."""
+
+    _kind = "fir"
 
     def __init__(self, coeffs, channels: int = 1, device: int = DEVICE):
         self.coeffs = f64(coeffs).ravel()
-        self.channels = int(channels)
-        self._h = C.c_void_p()
-        check(lib().ad_fir_create(ptr(self.coeffs), self.coeffs.size, self.channels, int(device),
-                                  C.byref(self._h)))
+        self._create(channels, device, ptr(self.coeffs), self.coeffs.size)
 
     def ProcessBlock(self, buf):  # :74-114
         b = _as2d(buf, self.channels)
@@ -2087,22 +1536,8 @@ class Filter:
 
     def process_device(self, d_src: int, src_stride: int, d_dst: int, dst_stride: int, n: int,
                        stream: int | None = None):
-        check(lib().ad_fir_process_device(self._h, C.c_void_p(d_src), int(src_stride), C.c_void_p(d_dst),
-                                          int(dst_stride), int(n), C.c_void_p(stream or 0)))
-
-    def Reset(self):
-        check(lib().ad_fir_reset(self._h))
-
-    def close(self):
-        if self._h:
-            lib().ad_fir_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        check(self._device_fn(self._h, C.c_void_p(d_src), int(src_stride), C.c_void_p(d_dst), int(dst_stride), int(n),
+                              C.c_void_p(stream or 0)))
 
 
 def chain_process(coeffs, state, gain, buf):
