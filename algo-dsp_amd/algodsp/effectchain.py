@@ -26,7 +26,9 @@ dyn-transient, spectral-freeze and pitch-spectral (whose structures point at the
 Hann table and the resampling prototype computed here).  With
 Chain(sidechain=True) the dyn-lookahead and vocoder nodes run as well: their
 structures (ad_fx_lookahead_node, ad_fx_vocoder_node) carry the effect's config
-and the side parents, the edges with toPortIndex 1.
+and the side parents, the edges with toPortIndex 1.  With
+Chain(pitch_time=True) the pitch-time node runs too (ad_pitchtime_config,
+whose structure lives in algodsp.pitch).
 """
 from __future__ import annotations
 
@@ -54,6 +56,7 @@ FXN_DISTORTION, FXN_BITCRUSHER = 15, 16  # 14 is not assigned
 FXN_DEESSER, FXN_TRANSIENT = 18, 19  # 17 is not assigned
 FXN_SPECFREEZE, FXN_PITCHSPEC = 20, 21
 FXN_LOOKAHEAD, FXN_VOCODER = 23, 24  # 22 is not assigned
+FXN_PITCHTIME = 25
 SIDECHAIN_TYPES = ("dyn-lookahead", "vocoder")  # splitMainAndSideParents chain_process.go:128
 MAX_PARENTS = 8
 
@@ -510,6 +513,26 @@ def spectral_pitch_params(p: Params, fs: float):
     return c, w, taps
 
 
+def time_pitch_params(p: Params, fs: float):
+    """timePitchRuntime.Configure (runtime_filter_pitch_reverb.go:226-242) and configureTimePitch
+    (configure.go:348-370) on a NewPitchShifter(fs): (config, its fade-in table)."""
+    from . import pitch
+
+    seq = clamp(p.GetNum("sequence", 40), 20, 120)
+    ov = clamp(p.GetNum("overlap", 10), 4, 60)
+    if ov >= seq:
+        ov = seq - 1
+    ratio = math.pow(2, clamp(p.GetNum("semitones", 0), -24, 24) / 12.0)  # SetPitchSemitones
+    # the factory builds NewPitchShifter(fs) with its defaults first, and the setters run in configureTimePitch's
+    # order, each rebuilding with the values set so far: a sample rate one of those steps refuses fails there
+    steps = [pitch.DEFAULT_SEQUENCE_MS, pitch.DEFAULT_OVERLAP_MS, pitch.DEFAULT_SEARCH_MS]
+    pitch.frame_lengths(fs, *steps)
+    for k, v in enumerate((seq, ov, clamp(p.GetNum("search", 15), 2, 40))):
+        steps[k] = v
+        pitch.frame_lengths(fs, *steps)
+    return pitch.make_config(fs, ratio, *steps)
+
+
 def lookahead_params(p: Params, fs: float) -> LookaheadConfig:
     """lookaheadLimiterRuntime.Configure (runtime_dynamics.go:94-116) on NewLookaheadLimiter(fs)."""
     cfg = LookaheadConfig()
@@ -615,11 +638,16 @@ class Chain:
     `ir_provider` is effectchain.WithIRProvider's IRProvider (GetIR(index) ->
     (samples [ch][n], sample_rate, ok)) for reverb-conv nodes.  `sidechain=True`
     admits the dyn-lookahead and vocoder nodes and routes their toPortIndex 1
-    edges to the side input; the default keeps both types UnknownEffect."""
+    edges to the side input; the default keeps both types UnknownEffect.
+    `pitch_time=True` admits the pitch-time node (algodsp.pitch, the WSOLA pitch
+    shifter); the default keeps it UnknownEffect.  That node transforms each
+    call's whole block, so its result depends on the length of the call, as the
+    reference's does on its block."""
 
     def __init__(self, sample_rate: float = 48000.0, channels: int = 1, designer=None, device: int = 0,
-                 ir_provider=None, sidechain: bool = False):
+                 ir_provider=None, sidechain: bool = False, pitch_time: bool = False):
         self.sample_rate = float(sample_rate)
+        self.pitch_time = bool(pitch_time)  # opt-in, as sidechain is, for the same reason
         # the dyn-lookahead and vocoder nodes, with their side inputs, run on the GPU only where the caller asks:
         # a caller that takes UnknownEffect as "run this graph on the reference" keeps getting it for them
         self.sidechain = bool(sidechain)
@@ -825,6 +853,13 @@ class Chain:
                 cfgs[i].config, cfgs[i].bytes = C.addressof(cfg), C.sizeof(cfg)
                 sd.update(type="pitchspec", pitchspec={f: getattr(cfg, f) for f, _ in cfg._fields_
                                                        if f not in ("window", "resample_taps")})
+            elif t == "pitch-time" and self.pitch_time:
+                d.type = FXN_PITCHTIME
+                cfg, fade = time_pitch_params(p, fs)
+                keep += [cfg, fade]
+                cfgs[i].config, cfgs[i].bytes = C.addressof(cfg), C.sizeof(cfg)
+                sd.update(type="pitchtime", pitchtime={f: getattr(cfg, f) for f, _ in cfg._fields_
+                                                       if f not in ("fade_in", "fade_len")})
             elif sidechain:
                 lookahead = t == "dyn-lookahead"
                 d.type = FXN_LOOKAHEAD if lookahead else FXN_VOCODER

@@ -26,7 +26,7 @@
 //   * the reverbs other than Freeverb, the delays and the modulation effects
 //     (flanger, phaser, tremolo, ringmod) and the waveshapers (distortion,
 //     dist-cheb, bitcrusher), the de-esser, the transient shaper, the spectral
-//     freeze and the spectral pitch shifter are ops of their own on their
+//     freeze and the two pitch shifters are ops of their own on their
 //     handles;
 //   * the lookahead limiter and the vocoder are ops that rewrite the node's
 //     buffer in place and read a second, side buffer (op.srcs): the mix of the
@@ -45,6 +45,7 @@
 
 #include "ad_common.hpp"
 #include "dsp_kernels.hpp"
+#include "pitchtime_kernels.hpp"
 
 using namespace adsp;
 
@@ -313,6 +314,10 @@ const NodeType kNodeTypes[] = {
      create<ad_vocoder, ad_vocoder_config, ad_vocoder_create, ad_vocoder_process_device, ad_vocoder_reset,
             ad_vocoder_destroy>,
      "fx graph: vocoder node without a valid config of its size"},
+    {AD_FXN_PITCHTIME, FxOp::HANDLE, in_cfg<ad_pitchtime_config>, valid<ad_pitchtime_config, pitchtime_validate>,
+     create<PitchTime, ad_pitchtime_config, pitchtime_create, pitchtime_process_device, pitchtime_reset,
+            pitchtime_destroy>,
+     "fx graph: time-domain pitch shifter node without a valid config of its size"},
 };
 const NodeType* node_type(int type) {
   for (const NodeType& t : kNodeTypes)

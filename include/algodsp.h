@@ -567,7 +567,9 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
  *                      runtime_filter_pitch_reverb.go:274-303) and
  *   AD_FXN_PITCHSPEC   pitch.SpectralPitchShifter.ProcessInPlace (pitch-spectral,
  *                      runtime_filter_pitch_reverb.go:248-272), configured through
- *                      ad_fx_graph_create_cfg.
+ *                      ad_fx_graph_create_cfg, and
+ *   AD_FXN_PITCHTIME   pitch.PitchShifter.ProcessInPlace (pitch-time,
+ *                      runtime_filter_pitch_reverb.go:222-246), configured the same way.
  * The result is the output node's buffer.  Linear runs of in-place nodes fuse
  * into one launch (bit-identical, see capi_fxgraph.cpp).  Other node types
  * return AD_ERR_UNKNOWN_EFFECT; the configs are copied at create.          */
@@ -604,6 +606,10 @@ void ad_fx_chain_destroy(ad_fx_chain* h);
                                 of its own that reads its side parents */
 #define AD_FXN_VOCODER 24    /* vocoder: an ad_vocoder created from cfg[i] (an ad_fx_vocoder_node); the node's
                                 buffer is the modulator, the side parents mix into the carrier */
+#define AD_FXN_PITCHTIME 25  /* pitch-time: pitch.PitchShifter.ProcessInPlace (runtime_filter_pitch_reverb.go:222-246)
+                                configured by cfg[i], an ad_pitchtime_config, see below (its fade-in table is read
+                                at create), an op of its own.  The node has no handle type and no entry points of its
+                                own: a graph of input -> pitch-time -> output is the processor */
 #define AD_FX_MAX_PARENTS 8
 struct ad_fdn_config;
 struct ad_delay_config;
@@ -1547,6 +1553,35 @@ int ad_pitchspec_process_device(ad_pitchspec* p, double* d_buf, int64_t stride, 
 int ad_pitchspec_reset(ad_pitchspec* p);
 int ad_pitchspec_profile(ad_pitchspec* p, int enable, double* ms);
 void ad_pitchspec_destroy(ad_pitchspec* p);
+
+/* ---- time-domain pitch shifter (dsp/effects/pitch/pitch_shifter.go) ----------
+ * pitch.PitchShifter for `channels` channels: a WSOLA stretch (timeStretch
+ * :298-357; per frame a normalised cross-correlation over 2 searchLen + 1
+ * candidates, findBestOverlap :359-389) and a 4-point Hermite resample back to
+ * the call's length (:391-430).  Every candidate's sums keep the reference's
+ * term order, so the selections, and with them every sample, are the
+ * reference's bit for bit.  The processor is stateless: a call transforms its
+ * whole block, and the result depends on the length of the call as the
+ * reference's does on its block.  |ratio - 1| <= 1e-9 leaves the buffer.
+ *
+ * It runs as the node AD_FXN_PITCHTIME of an fx graph and has no entry points
+ * of its own: cfg[i] of the node is this structure with its size, through the
+ * graph's cfg create call above.  The ranges are the reference's setters' and
+ * rebuild's (:122-217, :252-276): ratio in [0.25, 4], sequence in [20, 120] ms,
+ * overlap in [4, 60] ms and below the sequence, search in [2, 40] ms; the
+ * lengths are max(round(ms * 0.001 * sample_rate), 32 / 8 / 1) with
+ * overlapLen < sequenceLen and a hop of at least 4; a sample rate that makes
+ * the sequence longer than 2^24 samples is refused as well.  Anything else is
+ * AD_ERR_INVALID_ARGUMENT at create.  fade_in is the cross-fade's rising half,
+ * [fade_len] with fade_len == overlapLen, read at create; NULL (fade_len is
+ * then not read) has the library compute 0.5 - 0.5 cos(pi i / (L - 1)) with
+ * its own cos.  A call takes n < 2^29 samples per channel. */
+typedef struct ad_pitchtime_config {
+  double sample_rate, pitch_ratio;
+  double sequence_ms, overlap_ms, search_ms;
+  const double* fade_in; /* [fade_len], or NULL */
+  int64_t fade_len;
+} ad_pitchtime_config;
 
 /* ---- spectral correlation / deconvolution (dsp/conv/correlate.go,
  * dsp/conv/deconvolve.go) --------------------------------------
