@@ -30,6 +30,34 @@ static_assert(N1 % kRowsPerInstr == 0, "whole load rounds");
 // there, so A keeps fft_run.
 static_assert(ColPlan::T <= 64 && 64 % ColPlan::T == 0, "a column transform sits inside one wave");
 
+// Tile I/O of A and C.  Thread (r0, col) = (tid / W, tid % W) holds rows r0 +
+// kRowsPerInstr i of column col, so access instruction i covers tile rows
+// kRowsPerInstr i .. + kRowsPerInstr - 1: its place against the signal or the
+// output is the same for all lanes and is classified from scalars
+// (long_tile_bounds): an instruction inside the range is a plain access, one
+// outside is not issued, only a straddling one tests per lane.  Rows are
+// stepped through a scalar base with one 32-bit offset per thread.  On the LDS
+// side row r0 + kRowsPerInstr i has slot lds_slot(r0) ^ lds_slot(kRowsPerInstr i)
+// (disjoint bits): one swizzle per thread.
+static_assert(kRowsPerInstr == 16 && kRowsPerInstr == kLongTileRows, "lds_slot_split16: r0 is the low nibble of the row");
+static_assert(N1 / 2 % kRowsPerInstr == 0, "row N1/2 is instruction N1/2 / kRowsPerInstr of r0 = 0");
+constexpr int kHalfInstr = N1 / 2 / kRowsPerInstr;  // instructions over rows 0 .. N1/2 - 1; row N1/2 is r0 = 0 of one more
+
+// Slot of the mirror row (N1 - k1) mod N1 of k1 = r0 + kRowsPerInstr i, i <
+// kHalfInstr.  Its low nibble (16 - r0) mod 16 is the thread's own (sm its
+// swizzle) and above it stands 16 h, h = 31 - i; r0 = 0 borrows nothing and
+// has 16 (h + 1) with nibble 0 (row 0 mirrors itself).  The swizzle of 16 h
+// depends on h mod 8 only, so a thread has eight such bases, each a select
+// between two forms, and every access adds its 16 h as a constant.
+__device__ __forceinline__ int mirror_slot(int sm, int r0, int i) {
+  constexpr int kTop = N1 / kRowsPerInstr - 1;
+  const int h = kTop - i, k = h & 7;
+  const int base = r0 ? (sm ^ (lds_slot(kRowsPerInstr * k) & 15))
+                      : kRowsPerInstr + (lds_slot(kRowsPerInstr * ((k + 1) & 7)) & 15);
+  if (i == 0) return r0 ? kRowsPerInstr * h + base : 0;
+  return kRowsPerInstr * h + base;
+}
+
 __global__ __launch_bounds__(kColThreads) void k_long_cols_fwd(LongColArgs a) {
   __shared__ double2 lds[(W / 2) * FS];
   __shared__ double2 ltab[TwSplit<N1>::N];
@@ -39,18 +67,32 @@ __global__ __launch_bounds__(kColThreads) void k_long_cols_fwd(LongColArgs a) {
   const int tile = item % kTiles, cb = item / kTiles;
   const int c = cb / a.blocks, j = cb % a.blocks;
   const int col = tid % W, r0 = tid / W;
-  const int64_t b0 = a.start + (int64_t)j * a.hop + tile * W + col;
-  const double* x = a.x + (int64_t)c * a.x_stride;
+  const int64_t origin = a.start + (int64_t)j * a.hop;  // signal index of the block's point 0
+  const LongBlockRange rng = long_block_range(origin, 0, a.n);
+  const LongTileBounds tb = long_tile_bounds(tile, rng);
+  const double* x = a.x + (int64_t)c * a.x_stride + origin;  // the block's point 0
+  const unsigned xoff = r0 * N2 + col;
   double in[N1 / kRowsPerInstr];
 #pragma unroll
   for (int i = 0; i < N1 / kRowsPerInstr; ++i) {
-    const int64_t idx = b0 + (int64_t)(r0 + kRowsPerInstr * i) * N2;
-    in[i] = (idx >= 0 && idx < a.n) ? x[idx] : 0.0;
+    const int first = long_tile_first(tile, i);
+    if (long_tile_inside(i, tb)) {
+      in[i] = (x + first)[xoff];
+    } else if (long_tile_touched(i, tb)) {
+      // no branch per lane: a lane outside reads the range's first point and drops it
+      const int e = first + (int)xoff;
+      const bool ok = long_point_valid(e, rng);
+      const double xe = x[ok ? e : rng.lo];
+      in[i] = ok ? xe : 0.0;
+    } else {
+      in[i] = 0.0;
+    }
   }
   const TwLds<N1> tw = tw_lds_compute<N1>(ltab, tid, kColThreads);
   double* img = reinterpret_cast<double*>(lds + (col >> 1) * FS) + (col & 1);
+  const int sk = lds_slot(r0);
 #pragma unroll
-  for (int i = 0; i < N1 / kRowsPerInstr; ++i) img[2 * lds_slot(r0 + kRowsPerInstr * i)] = in[i];
+  for (int i = 0; i < N1 / kRowsPerInstr; ++i) img[2 * lds_slot_split16(sk, kRowsPerInstr * i)] = in[i];
   __syncthreads();
   const int f = tid / ColPlan::T, t = tid % ColPlan::T;
   double2* my = lds + f * FS;
@@ -64,19 +106,33 @@ __global__ __launch_bounds__(kColThreads) void k_long_cols_fwd(LongColArgs a) {
   for (int s = 0; s < 16; ++s) my[last_pass_slot<N1, 16>(t, s)] = v[s];
   __syncthreads();
   // separation of the two real columns: even col a = (Z[k] + conj Z[-k]) / 2,
-  // odd col b = (Z[k] - conj Z[-k]) / 2i
+  // odd col b = (Z[k] - conj Z[-k]) / 2i.  The image reads of a batch of rows
+  // are issued together, ahead of the batch's stores.
   const double2* zc = lds + (col >> 1) * FS;
-  double2* T = a.T + (int64_t)cb * kLongRows * kLongPitch + tile * W + col;
+  const int sm = lds_slot((kRowsPerInstr - r0) & (kRowsPerInstr - 1));
+  double2* T = a.T + (int64_t)cb * kLongRows * kLongPitch + tile * W;
+  const unsigned toff = r0 * kLongPitch + col;
+  const auto separate = [col](double2 zk, double2 zm) {
+    return (col & 1) ? make_double2(0.5 * (zk.y + zm.y), 0.5 * (zm.x - zk.x))
+                     : make_double2(0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y));
+  };
+  constexpr int kBatch = 8;
+  static_assert(kHalfInstr % kBatch == 0, "whole batches");
 #pragma unroll
-  for (int i = 0; i <= N1 / 2 / kRowsPerInstr; ++i) {
-    const int k1 = r0 + kRowsPerInstr * i;
-    if (k1 <= N1 / 2) {
-      const double2 zk = zc[lds_slot(k1)];
-      const double2 zm = zc[lds_slot((N1 - k1) & (N1 - 1))];
-      const double2 o = (col & 1) ? make_double2(0.5 * (zk.y + zm.y), 0.5 * (zm.x - zk.x))
-                                  : make_double2(0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y));
-      st2<true>(T + (int64_t)k1 * kLongPitch, o);
+  for (int b = 0; b < kHalfInstr; b += kBatch) {
+    double2 zk[kBatch], zm[kBatch];
+#pragma unroll
+    for (int u = 0; u < kBatch; ++u) {
+      zk[u] = zc[lds_slot_split16(sk, kRowsPerInstr * (b + u))];
+      zm[u] = zc[mirror_slot(sm, r0, b + u)];
     }
+#pragma unroll
+    for (int u = 0; u < kBatch; ++u)
+      st2<true>(T + (int64_t)(b + u) * kRowsPerInstr * kLongPitch + toff, separate(zk[u], zm[u]));
+  }
+  if (r0 == 0) {  // row N1/2, its own mirror
+    const double2 zh = zc[lds_slot(N1 / 2)];
+    st2<true>(T + (int64_t)(N1 / 2) * kLongPitch + toff, separate(zh, zh));
   }
 }
 
@@ -89,31 +145,33 @@ __global__ __launch_bounds__(kColThreads) void k_long_cols_inv(LongColArgs a) {
   const int tile = item % kTiles, cb = item / kTiles;
   const int c = cb / a.blocks, j = cb % a.blocks;
   const int col = tid % W, r0 = tid / W;
-  const double2* T = a.T + (int64_t)cb * kLongRows * kLongPitch + tile * W + col;
-  constexpr int NI = N1 / 2 / kRowsPerInstr + 1;
-  double2 in[NI];
+  const double2* T = a.T + (int64_t)cb * kLongRows * kLongPitch + tile * W;
+  const unsigned toff = r0 * kLongPitch + col;
+  double2 in[kHalfInstr + 1];
 #pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int k1 = r0 + kRowsPerInstr * i;
-    in[i] = k1 <= N1 / 2 ? ld2<true>(T + (int64_t)k1 * kLongPitch) : make_double2(0, 0);
-  }
+  for (int i = 0; i < kHalfInstr; ++i) in[i] = ld2<true>(T + (int64_t)i * kRowsPerInstr * kLongPitch + toff);
+  in[kHalfInstr] = r0 == 0 ? ld2<true>(T + (int64_t)(N1 / 2) * kLongPitch + toff) : make_double2(0, 0);  // row N1/2
   const TwLds<N1> tw = tw_lds_compute<N1>(ltab, tid, kColThreads);
   // Z = Va + i Vb over all N1 rows, rows above N1/2 from the mirror
   // (V[N1 - k] = conj V[k]: the columns are real).  The even lane of a column
-  // pair writes row k, the odd lane row N1 - k.
+  // pair writes row k, the odd lane row N1 - k; rows 0 and N1/2 (r0 = 0 of the
+  // first and the last instruction) are real and have no mirror to write.
   double2* zc = lds + (col >> 1) * FS;
+  const int sk = lds_slot(r0);
+  const int sm = lds_slot((kRowsPerInstr - r0) & (kRowsPerInstr - 1));
+  const bool even = !(col & 1);
 #pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int k1 = r0 + kRowsPerInstr * i;
-    const double px = __shfl_xor(in[i].x, 1);
-    const double py = __shfl_xor(in[i].y, 1);
-    if (k1 <= N1 / 2) {
-      if (!(col & 1)) {  // Va = in, Vb = partner
-        const bool edge = k1 == 0 || k1 == N1 / 2;
-        zc[lds_slot(k1)] = edge ? make_double2(in[i].x, px) : make_double2(in[i].x - py, in[i].y + px);
-      } else if (k1 != 0 && k1 != N1 / 2) {  // Va = partner, Vb = in
-        zc[lds_slot(N1 - k1)] = make_double2(px + in[i].y, in[i].x - py);
-      }
+  for (int i = 0; i <= kHalfInstr; ++i) {
+    const double px = lane_xor1(in[i].x);
+    const double py = lane_xor1(in[i].y);
+    if (i == kHalfInstr) {
+      if (even && r0 == 0) zc[lds_slot(N1 / 2)] = make_double2(in[i].x, px);
+    } else if (even) {  // Va = in, Vb = partner
+      const bool edge = i == 0 && r0 == 0;
+      zc[lds_slot_split16(sk, kRowsPerInstr * i)] =
+          edge ? make_double2(in[i].x, px) : make_double2(in[i].x - py, in[i].y + px);
+    } else if (i != 0 || r0 != 0) {  // Va = partner, Vb = in
+      zc[mirror_slot(sm, r0, i)] = make_double2(px + in[i].y, in[i].x - py);
     }
   }
   __syncthreads();
@@ -130,17 +188,33 @@ __global__ __launch_bounds__(kColThreads) void k_long_cols_inv(LongColArgs a) {
   __syncthreads();  // the stores below read across the images
   // 8-byte stores, runs of W per row.  The per-row 16-byte pair scheme K3 uses
   // for rows off alignment was measured here and is slower (DESIGN.md §2:
-  // C 154 us against 124 us, the step 0.418 against 0.385 ms).
+  // C 154 us against 124 us, the step 0.418 against 0.385 ms).  The image
+  // reads of the instructions inside the block's outputs are issued together,
+  // ahead of their stores.
   const double* img = reinterpret_cast<const double*>(zc) + (col & 1);
   double* y = a.y + (int64_t)c * a.y_stride;
-  const int64_t o0 = (int64_t)j * a.hop - a.skip + tile * W + col;  // output index of the column's row 0
   const int64_t lo = (int64_t)j * a.hop;
   const int64_t hi = a.out_len < lo + a.hop ? a.out_len : lo + a.hop;
+  const int64_t origin = lo - a.skip;  // output index of the block's point 0
+  const LongBlockRange rng = long_block_range(origin, lo, hi);
+  const LongTileBounds tb = long_tile_bounds(tile, rng);
+  y += origin;
+  const unsigned yoff = r0 * N2 + col;
+  double out[N1 / kRowsPerInstr];
 #pragma unroll
-  for (int i = 0; i < N1 / kRowsPerInstr; ++i) {
-    const int r = r0 + kRowsPerInstr * i;
-    const int64_t o = o0 + (int64_t)r * N2;
-    if (o >= lo && o < hi) y[o] = img[2 * lds_slot(r)];
+  for (int i = 0; i < N1 / kRowsPerInstr; ++i)
+    if (long_tile_inside(i, tb)) out[i] = img[2 * lds_slot_split16(sk, kRowsPerInstr * i)];
+#pragma unroll
+  for (int i = 0; i < N1 / kRowsPerInstr; ++i)
+    if (long_tile_inside(i, tb)) (y + long_tile_first(tile, i))[yoff] = out[i];
+  // The one or two instructions an end of the range cuts through, per lane.  A
+  // loop that is not unrolled (unrolled into the loop above, the compiler folds
+  // the two cases into one masked store per instruction).
+#pragma unroll 1
+  for (int i = long_tile_next_straddling(tb.any_first - 1, tb); i < tb.any_first + tb.any_count;
+       i = long_tile_next_straddling(i, tb)) {
+    const int first = long_tile_first(tile, i);
+    if (long_point_valid(first + (int)yoff, rng)) (y + first)[yoff] = img[2 * lds_slot(r0 + kRowsPerInstr * i)];
   }
 }
 

@@ -24,6 +24,78 @@ constexpr int64_t kLongN = (int64_t)kLongN1 * kLongN2;
 constexpr int kLongRows = kLongN1 / 2 + 1;
 constexpr int kLongPitch = kLongN2 + 8;  // row pitch of T and H, off the power of two
 
+// Bounds of the tile I/O of A and C.  Point e of a block, 0 <= e < kLongN, is
+// element origin + e of the signal (A) or of the output (C), valid in [lo, hi).
+// long_block_range() turns that into the block's own terms once per item:
+// valid <=> r.lo <= e < r.hi, in 32 bits.
+//
+// One global load or store instruction of a tile covers kLongTileRows rows of
+// kLongW columns: instruction i of tile `tile` holds the points first + kLongN2
+// r + col, r < kLongTileRows, col < kLongW, first = kLongW tile + kLongTileStep
+// i.  It is wholly inside the range (no per-lane test) iff first >= r.lo and
+// first + kLongTileSpan < r.hi, wholly outside (no access) iff first +
+// kLongTileSpan < r.lo or first >= r.hi, and takes the per-lane test otherwise.
+// Both conditions are runs of i, which long_tile_bounds() works out once per
+// item from scalars; long_tile_class() is then one unsigned compare per run.
+// kLongTileStep > kLongTileSpan, so the spans of an item's instructions are
+// disjoint and each end of the range makes at most one of them straddle.
+constexpr int kLongTileRows = 256 / kLongW;
+constexpr int kLongTileStepLog2 = 16;
+constexpr int kLongTileStep = kLongTileRows * kLongN2;                     // from one instruction's first point to the next's
+constexpr int kLongTileSpan = (kLongTileRows - 1) * kLongN2 + kLongW - 1;  // from its first point to its last
+static_assert(kLongTileStep == 1 << kLongTileStepLog2, "long_tile_bounds divides by shifting");
+struct LongBlockRange {
+  int lo, hi;
+};
+__host__ __device__ constexpr LongBlockRange long_block_range(int64_t origin, int64_t lo, int64_t hi) {
+  const int64_t a = lo - origin, b = hi - origin;
+  const int l = (int)(a < 0 ? 0 : a > kLongN ? kLongN : a);
+  const int h = (int)(b < 0 ? 0 : b > kLongN ? kLongN : b);
+  return h > l ? LongBlockRange{l, h} : LongBlockRange{0, 0};
+}
+__host__ __device__ constexpr bool long_point_valid(int e, LongBlockRange r) {
+  return (unsigned)(e - r.lo) < (unsigned)(r.hi - r.lo);
+}
+// instructions in_first .. + in_count - 1 are inside, those of any_first .. +
+// any_count - 1 touch the range at all (the arithmetic shift is a floor)
+struct LongTileBounds {
+  int in_first, in_count, any_first, any_count;
+};
+__host__ __device__ constexpr LongTileBounds long_tile_bounds(int tile, LongBlockRange r) {
+  const int t = tile * kLongW;
+  const int in_first = (r.lo - t + kLongTileStep - 1) >> kLongTileStepLog2;
+  const int in_last = (r.hi - 1 - kLongTileSpan - t) >> kLongTileStepLog2;
+  const int any_first = (r.lo - kLongTileSpan - t + kLongTileStep - 1) >> kLongTileStepLog2;
+  const int any_last = (r.hi - 1 - t) >> kLongTileStepLog2;
+  const int in_count = in_last - in_first + 1, any_count = any_last - any_first + 1;
+  return {in_first, in_count > 0 ? in_count : 0, any_first, any_count > 0 ? any_count : 0};
+}
+__host__ __device__ constexpr bool long_tile_inside(int i, LongTileBounds b) {
+  return (unsigned)(i - b.in_first) < (unsigned)b.in_count;
+}
+__host__ __device__ constexpr bool long_tile_touched(int i, LongTileBounds b) {
+  return (unsigned)(i - b.any_first) < (unsigned)b.any_count;
+}
+// the touched instructions that are not inside, in rising order: the one after i
+// (start from any_first - 1, stop at any_first + any_count)
+__host__ __device__ constexpr int long_tile_next_straddling(int i, LongTileBounds b) {
+  ++i;
+  return b.in_count > 0 && i == b.in_first ? i + b.in_count : i;
+}
+enum LongTileClass : int { kLongTileInside = 0, kLongTileOutside = 1, kLongTileStraddle = 2 };
+__host__ __device__ constexpr LongTileClass long_tile_class(int i, LongTileBounds b) {
+  return long_tile_inside(i, b) ? kLongTileInside : long_tile_touched(i, b) ? kLongTileStraddle : kLongTileOutside;
+}
+__host__ __device__ constexpr int long_tile_first(int tile, int i) { return tile * kLongW + i * kLongTileStep; }
+// C at K = 131072 (skip = 31 rows and 4095 columns), a full block: the first
+// stored point is the last element of instruction 1 of the last tile
+static_assert(long_tile_class(1, long_tile_bounds(kLongN2 / kLongW - 1, long_block_range(-131071, 0, kLongN - 131071))) ==
+                      kLongTileStraddle &&
+                  long_tile_class(1, long_tile_bounds(kLongN2 / kLongW - 2, long_block_range(-131071, 0, kLongN - 131071))) ==
+                      kLongTileOutside &&
+                  long_tile_class(2, long_tile_bounds(0, long_block_range(-131071, 0, kLongN - 131071))) == kLongTileInside,
+              "tile bounds at the bench's own skip");
+
 struct LongColArgs {
   // A: block j of row c reads x[c][start + j hop + i], i < N; indices outside [0, n) are zeros
   const double* x;

@@ -204,6 +204,22 @@ __device__ __forceinline__ int lds_slot(int i) {
 // one swizzle per butterfly and one XOR per access instead of the shift / mask
 // chain per access.
 __device__ __forceinline__ int lds_slot_split(int swz_base, int off) { return swz_base ^ lds_slot(off); }
+// The same for a base below 16 and an offset that is a multiple of 16: the
+// swizzle moves the low nibble only, so the offset's own bits add on and, with
+// the offset known at compile time, can ride in the instruction's offset field.
+__device__ __forceinline__ int lds_slot_split16(int swz_base, int off16) {
+  return off16 + (swz_base ^ (lds_slot(off16) & 15));
+}
+
+// x of lane ^ 1: the DPP quad permute [1, 0, 3, 2], on the vector pipe (a
+// __shfl_xor goes through the LDS pipe as ds_bpermute).  Call it with every
+// lane of the quad active.
+__device__ __forceinline__ double lane_xor1(double x) {
+  constexpr int kQuadPerm1032 = 1 | (0 << 2) | (3 << 4) | (2 << 6);
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), kQuadPerm1032, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), kQuadPerm1032, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
 // Twiddle-table slot: stride-8 reads (the NS = 64 pass at M = 4096) and
 // consecutive reads both spread over 16 slots.
 __device__ __forceinline__ int tw_slot(int i) { return i ^ ((i >> 3) & 7); }
